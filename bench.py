@@ -14,11 +14,24 @@ channels on its own GPU (weak scaling); there is no data-path collective.  The
 ranks only meet for the barrier around the timed region and a MAX over elapsed
 times.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line; everything
+else the benchmark measures or checks runs only with --full:
+
+  --full          the oracle check of the bench's own output (--verify), single
+                  launches sampled behind the timed region, the plain read / write
+                  stream kernels, PMC traffic and SQ summaries, end-to-end and
+                  single-block latency, the other configurations (`configs`), the
+                  N > 1 scatter and config 4 legs and `cpu_baseline`
+  --dump-outputs DIR
+                  after the timed steps, what the timed path's last step wrote (PCM,
+                  PCM counts, ...) as DIR/<name>.npy in float32; arrays of more than
+                  4M elements as a fixed seeded sample of 4M of them
+
 Extra objects in the JSON line:
   roofline      algorithmic HBM bytes per launch / mean duration of the dominant
                 kernel, measured with HIP events on the launch stream during the
                 timed region, against the 8 TB/s HBM3E peak
-  cpu_baseline  the reference's own CPU chain (oracle/_ref, compiled from the
+  cpu_baseline  (--full) the reference's own CPU chain (oracle/_ref, compiled from the
                 reference sources) timed on this box's host cores on a bounded
                 sample of the same workload (rank 0, N=1 only)
 """
@@ -172,6 +185,31 @@ def cpu_baseline_port(seconds, threads, x):
     }
 
 
+DUMP_MAX_ELEMS = 1 << 22        # --dump-outputs: per array; at most four arrays of 16 MB in float32
+
+
+def snapshot_outputs(tensors):
+    """{name: device tensor} -> {name: float32 numpy array}: the whole tensor, or a fixed sample of DUMP_MAX_ELEMS of its
+    elements (seeded, a function of its size alone: two builds run with the same arguments sample the same positions),
+    gathered on the device.  Called right behind the timed region, before anything else launches into the buffers."""
+    out = {}
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.unique(np.random.default_rng(20260101).integers(0, t.numel(), size=DUMP_MAX_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.to(torch.float32).cpu().numpy()
+    return out
+
+
+def write_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    print(f"bench.py: wrote {', '.join(sorted(arrays))} to {directory}", file=sys.stderr)
+
+
 def spin_until_done(event, limit_s=120.0):
     """Polls the event that closes the timed region until the GPU has passed it, so that the synchronize calls behind it
     (the contract's bracket) return at once: a blocking wait adds the host's wake-up latency -- tens of microseconds, ~1 %
@@ -188,9 +226,11 @@ MOD_KERNELS = {"ssbmod": "hrfd::k_mod<1>",
                "wbfmmod": "hrfd::k_mod<101> (x32 + Nco step), k_phase_rows8 (the serial Nco recurrence, nine time slices), hrfd::k_wb_tail (Nco lookup + x8)"}
 
 
-def measure_mod(api, shard, device, dist, workload, C, B, steps, warmup, settle, rank, world, extras=True):
+def measure_mod(api, shard, device, dist, workload, C, B, steps, warmup, settle, rank, world, extras=True,
+                sample_kernels=True, dump=None):
     """`C` modulators of one kind, `B` blocks of 512 PCM samples (64 ms) each per step -> int8 IQ at 2.048 MS/s
-    (BASELINE config 5 for 1024 SSB channels).  Unit of work: one output IQ sample."""
+    (BASELINE config 5 for 1024 SSB channels).  Unit of work: one output IQ sample.  `sample_kernels`: single calls
+    bracketed behind the timed region (min / median); `dump`: a dict that receives the last timed step's output."""
     n = 512 * B
     gen = torch.Generator(device=device)
     gen.manual_seed(7 + rank)
@@ -227,7 +267,9 @@ def measure_mod(api, shard, device, dist, workload, C, B, steps, warmup, settle,
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, device)
     m.sync()                                             # raises if a k_phase_scan wait expired
     region_ms = ev_region[0].elapsed_time(ev_region[1]) / steps
-    n_samp = min(4, steps)
+    if dump is not None:
+        dump.update(snapshot_outputs({"iq": out}))
+    n_samp = min(4, steps) if sample_kernels else 0
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_samp)]
     for a, b in ev:
         a.record(stream)
@@ -253,7 +295,7 @@ def measure_mod(api, shard, device, dist, workload, C, B, steps, warmup, settle,
                      "frac_of_measured_write": None if fill is None else round(achieved / fill, 4),
                      "kernel": MOD_KERNELS.get(workload, "k_am_rails / k_fm_step + k_phase_rows + k_fm_rails, then hrfd::k_mod<100>"),
                      "region_ms_per_launch": round(region_ms, 4), "priced_with": "region_ms_per_launch (one HIP event pair around the timed region / steps)",
-                     "kernel_ms_min": round(float(np.min(kernel_ms)), 4), "kernel_ms_median": round(float(np.median(kernel_ms)), 4),
+                     **({"kernel_ms_min": round(float(np.min(kernel_ms)), 4), "kernel_ms_median": round(float(np.median(kernel_ms)), 4)} if n_samp else {}),
                      "kernel_launches_sampled": n_samp, "algorithmic_bytes_per_launch": algo_bytes},
     }
 
@@ -262,13 +304,17 @@ def bench_mod(args, api, device, rank, world, dist):
     from hackrfdiags_amd import shard
     C, B = args.channels, args.blocks
     settle = max(0, SETTLE_STEPS - args.warmup)
+    dump = {} if args.dump_outputs and rank == 0 else None
     r = measure_mod(api, shard, device, dist, args.workload, C, B, args.steps, args.warmup, settle, rank, world,
-                    extras=not args.no_extras)
+                    extras=args.full and not args.no_extras, sample_kernels=args.full, dump=dump)
     kname = r["kname"]
-    t, src = pmc_traffic(f"{args.workload}_{C}x{B}")
-    r["roofline"]["traffic"] = t
-    r["roofline"]["traffic_source"] = src
-    r["roofline"]["traffic_over_algorithmic"] = None if t is None else round(t / r["roofline"]["algorithmic_bytes_per_launch"], 4)
+    if args.full:
+        t, src = pmc_traffic(f"{args.workload}_{C}x{B}")
+        r["roofline"]["traffic"] = t
+        r["roofline"]["traffic_source"] = src
+        r["roofline"]["traffic_over_algorithmic"] = None if t is None else round(t / r["roofline"]["algorithmic_bytes_per_launch"], 4)
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
     if rank == 0:
         print(json.dumps({
             "metric": f"IQ MSamples/s modulated (8 kS/s PCM -> 2.048 MS/s int8 IQ, {kname}) per GPU; % HBM roofline",
@@ -310,13 +356,16 @@ def bench_ingest(args, api, device, rank, world, dist):
     for i in range(args.steps):
         if i + 1 < args.steps:
             ing.acquire(); ing.submit(0)                 # batch i+1 travels while batch i is demodulated
-        ing.collect()
+        last = ing.collect()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, device)
     samples = C * B * (BLOCK // 2)
     value = world * samples * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, snapshot_outputs(
+            {k: torch.from_numpy(v.astype(np.int64)) for k, v in zip(("pcm", "pcm_count", "magnitude", "allowed"), last)}))
     if rank == 0:
         print(json.dumps({
             "metric": "IQ MSamples/s demodulated, host to host (pinned batches over PCIe, WBFM) per GPU",
@@ -379,6 +428,8 @@ def bench_fanout(args, api, device, rank, world):
     for _ in range(args.steps):
         step(times)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, snapshot_outputs({"pcm": pcm, "pcm_count": n_pcm}))
     sc, pr, co = (1e3 * float(np.mean([t[i] for t in times])) for i in range(3))
     samples = C * B * (BLOCK // 2)
     algo = C * B * (BLOCK + 1024 + 4)
@@ -759,10 +810,12 @@ def verify_against_oracle(iq, pcm, modes, launches, B, n, threshold, seed=0):
 
 def measure_rx(api, shard, device, dist, *, workload, C, B, signal, steps, warmup, settle, rank, world,
                scatter=False, quiet_fraction=0.0, threshold=None, iqdump=False, idle_s=0.0, serial_modes=False, stride_pad=0,
-               blk=BLOCK, verify=0):
+               blk=BLOCK, verify=0, sample_kernels=True, dump=None):
     """K timed steps of the receive path over one resident batch [C][B][262144]; returns the figures of a bench line.
     The dominant kernels' time comes from HIP events the library records on its launch stream(s) around the
-    demodulator kernels of every launch (hrfd_rx_debug_enable_timing)."""
+    demodulator kernels of every launch (hrfd_rx_debug_enable_timing).  `sample_kernels`: single launches timed
+    behind the region (always with the scatter, whose region holds the copies too); `dump`: a dict that receives
+    the last timed step's outputs."""
     gen = make_fm_batch if signal == "fmtone" else make_random_batch
     iq = gen(C, B, device, first_channel=rank * C)
     n_quiet = int(round(C * quiet_fraction))
@@ -809,7 +862,7 @@ def measure_rx(api, shard, device, dist, *, workload, C, B, signal, steps, warmu
     # each other with none) or every fourth one (round 4: 5 samples of 20 steps, and the gaps of the sampled ones still
     # inside the step time).  Single launches are still sampled -- min / median -- but BEHIND the timed region
     # (`n_samp` extra launches, hrfd_rx_debug_enable_timing): no event packet stands inside the region.
-    n_samp = min(8, steps)
+    n_samp = min(8, steps) if (sample_kernels or scatter) else 0
     rx.debug_enable_timing(0)
     def step():
         if scatter:
@@ -844,12 +897,15 @@ def measure_rx(api, shard, device, dist, *, workload, C, B, signal, steps, warmu
 
     rx.sync()
     region_ms = ev_region[0].elapsed_time(ev_region[1]) / steps
-    rx.debug_enable_timing(n_samp)
-    rx.debug_timing_every(1)
-    for _ in range(n_samp):
-        step()
-    stream.synchronize()
-    rx.sync()
+    if dump is not None:
+        dump.update(snapshot_outputs({"pcm": pcm, "pcm_count": n_pcm, "iq256": iq256}))
+    if n_samp:
+        rx.debug_enable_timing(n_samp)
+        rx.debug_timing_every(1)
+        for _ in range(n_samp):
+            step()
+        stream.synchronize()
+        rx.sync()
     counters = rx.debug_counters()
     kernel_ms = [rx.debug_kernel_ms(i) for i in range(n_samp)]
     produced = int(n_pcm.sum().item())
@@ -865,8 +921,8 @@ def measure_rx(api, shard, device, dist, *, workload, C, B, signal, steps, warmu
     out = {
         "value": world * samples_per_step * steps / elapsed / 1e6,            # MSamples/s, whole job
         "ms_per_step": 1e3 * elapsed / steps, "mean_ms": mean_ms, "achieved": achieved,
-        "kernel_ms_min": float(np.min(kernel_ms)), "kernel_ms_median": float(np.median(kernel_ms)),
-        "kernel_ms_sampled_mean": float(np.mean(kernel_ms)), "launches_sampled": n_samp,
+        "kernel_ms_min": float(np.min(kernel_ms)) if n_samp else None, "kernel_ms_median": float(np.median(kernel_ms)) if n_samp else None,
+        "kernel_ms_sampled_mean": float(np.mean(kernel_ms)) if n_samp else None, "launches_sampled": n_samp,
         "algo_bytes": algo_bytes, "counters": counters, "quiet_channels": n_quiet, "launches_timed": steps,
         "pcm_produced": produced, "pcm_expected": expect,
     }
@@ -1108,10 +1164,10 @@ def main():
                          "per-mode dispatch); ssbmod = config 5 (SSB modulator, 8-stage x256 interpolator)")
     ap.add_argument("--scatter", action="store_true",
                     help="N > 1 only: the HEADLINE's timed region includes the scatter of all IQ from rank 0 over RCCL "
-                         "(without this flag both legs are still measured and reported as `scatter`: `value` excludes it)")
+                         "(without this flag, --full still measures both legs and reports them as `scatter`: `value` excludes it)")
     ap.add_argument("--verify", type=int, default=16,
-                    help="receive workloads: after the timed region, this many channels of the bench's own batch go through the "
-                         "sequential CPU oracle and must match bit for bit (0: off)")
+                    help="receive workloads, with --full: after the timed region, this many channels of the bench's own batch go "
+                         "through the sequential CPU oracle and must match bit for bit (0: off)")
     ap.add_argument("--no-config4", action="store_true", help="N > 1: leave out the config 4 legs (4096 channels over the N GPUs)")
     ap.add_argument("--quiet-fraction", type=float, default=0.0,
                     help="this fraction of the channels carries no signal (with --threshold: their squelch gates close)")
@@ -1130,6 +1186,13 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="leave out the end-to-end and single-block latency figures and the `also` measurements "
                          "(profiling runs: only the headline launches in the kernel statistics)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures or checks: --verify, sampled single "
+                         "launches, the stream kernels' bandwidth, PMC / SQ summaries, end-to-end and single-block latency, "
+                         "`configs`, the N > 1 legs and the CPU baseline (a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path's last step computed as DIR/<name>.npy (float32; "
+                         "arrays of more than 4M elements as a fixed seeded sample)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1156,6 +1219,10 @@ def main():
 
     from hackrfdiags_amd import api, shard
 
+    if not args.full:
+        if args.verify and any(x == "--verify" or x.startswith("--verify=") for x in sys.argv[1:]):
+            print("bench.py: --verify is one of the --full extras: this plain run does not check against the oracle", file=sys.stderr)
+        args.verify = 0                                      # the oracle check is one of the --full extras
     if rank == 0 and args.verify and args.workload not in MOD_KINDS and args.workload not in ("ingest", "fanout"):
         # the checker is built and loaded BEFORE anything is measured (tests/reflib runs `make -C oracle` when the library is
         # stale): a broken checker must not cost the line its measurements
@@ -1181,23 +1248,55 @@ def main():
     # steps are measured at the clock a long-running stream sees, whatever W is.  (`configs.wbfm_256x16_unsettled`
     # is the figure without them.)
     settle = max(0, SETTLE_STEPS - args.warmup)
+    dump = {} if args.dump_outputs and rank == 0 else None
     r = measure_rx(api, shard, device, dist, workload=args.workload, C=C, B=B, signal=args.signal, steps=args.steps,
                    warmup=args.warmup, settle=settle, rank=rank, world=world, scatter=args.scatter,
                    quiet_fraction=args.quiet_fraction, threshold=args.threshold, iqdump=args.iqdump,
-                   serial_modes=args.serial_modes, stride_pad=args.stride_pad, verify=args.verify if rank == 0 else 0)
-    multi = multi_gpu_legs(api, shard, device, dist, args, r, C, B, settle, rank, world) if world > 1 else None
+                   serial_modes=args.serial_modes, stride_pad=args.stride_pad, verify=args.verify if rank == 0 else 0,
+                   sample_kernels=args.full, dump=dump)
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
+    multi = multi_gpu_legs(api, shard, device, dist, args, r, C, B, settle, rank, world) if world > 1 and args.full else None
     counters = r["counters"]
     assert r["pcm_produced"] == r["pcm_expected"], f"PCM samples produced {r['pcm_produced']} != {r['pcm_expected']}"
-    wname = rx_workload_name(args.workload, C, B, args.signal, args.quiet_fraction, args.iqdump)
-    traffic, traffic_src = pmc_traffic(wname)
-    read_gbs = stream_gbs(device, 0)
-    write_gbs = stream_gbs(device, 1)
-    # a read-only kernel cannot read faster than the kernel that does nothing else: if it does, a denominator is wrong
-    assert under_profiler() or rehearse or r["achieved"] <= read_gbs, \
-        f"{r['achieved']:.0f} GB/s algorithmic > {read_gbs:.0f} GB/s of the plain read kernel"
+    if args.full:
+        wname = rx_workload_name(args.workload, C, B, args.signal, args.quiet_fraction, args.iqdump)
+        traffic, traffic_src = pmc_traffic(wname)
+        read_gbs = stream_gbs(device, 0)
+        write_gbs = stream_gbs(device, 1)
+        # a read-only kernel cannot read faster than the kernel that does nothing else: if it does, a denominator is wrong
+        assert under_profiler() or rehearse or r["achieved"] <= read_gbs, \
+            f"{r['achieved']:.0f} GB/s algorithmic > {read_gbs:.0f} GB/s of the plain read kernel"
     value, achieved = r["value"], r["achieved"]
 
     if rank == 0:
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4)}
+        if args.full:
+            roofline.update({
+                "traffic": traffic,
+                "traffic_over_algorithmic": None if traffic is None else round(traffic / r["algo_bytes"], 4),
+                "traffic_source": traffic_src,
+            })
+        roofline.update({
+            "algorithmic_bytes_per_launch": r["algo_bytes"],
+            "kernel": headline_kernel_name(args),
+            "region_ms_per_launch": round(r["mean_ms"], 4),
+            "priced_with": "region_ms_per_launch: one HIP event pair on the launch stream around the %d launches of the timed region / steps "
+                           "(a throughput reciprocal: back-to-back launches)" % r["launches_timed"]
+                           + ("; kernel_ms_*: single launches bracketed BEHIND the region" if args.full else ""),
+        })
+        if args.full:
+            roofline.update({
+                "kernel_ms_min": round(r["kernel_ms_min"], 4),
+                "kernel_ms_median": round(r["kernel_ms_median"], 4),
+                "kernel_ms_sampled_mean": round(r["kernel_ms_sampled_mean"], 4),
+                "kernel_launches_sampled": r["launches_sampled"],
+                "measured_stream_read_GBps": round(read_gbs, 1),
+                "frac_of_measured_read": round(achieved / read_gbs, 4),
+                "measured_stream_write_GBps": round(write_gbs, 1),
+                "issue": issue_summary() if (args.workload == "wbfm" and C == 256 and B == 16) else None,
+            })
         line = {
             "metric": "IQ MSamples/s demodulated (2.048 MS/s->8 kS/s WBFM) per GPU; % HBM roofline",
             "value": round(value, 1),
@@ -1221,29 +1320,7 @@ def main():
             },
             "per_gpu_value": round(value / world, 1),
             "realtime_channels_per_gpu": int(value / world / 2.048),
-            "roofline": {
-                "bound": "hbm",
-                "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": traffic,
-                "traffic_over_algorithmic": None if traffic is None else round(traffic / r["algo_bytes"], 4),
-                "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": r["algo_bytes"],
-                "kernel": headline_kernel_name(args),
-                "region_ms_per_launch": round(r["mean_ms"], 4),
-                "priced_with": "region_ms_per_launch: one HIP event pair on the launch stream around the %d launches of the timed region / steps "
-                               "(a throughput reciprocal: back-to-back launches); kernel_ms_*: single launches bracketed BEHIND the region" % r["launches_timed"],
-                "kernel_ms_min": round(r["kernel_ms_min"], 4),
-                "kernel_ms_median": round(r["kernel_ms_median"], 4),
-                "kernel_ms_sampled_mean": round(r["kernel_ms_sampled_mean"], 4),
-                "kernel_launches_sampled": r["launches_sampled"],
-                "measured_stream_read_GBps": round(read_gbs, 1),
-                "frac_of_measured_read": round(achieved / read_gbs, 4),
-                "measured_stream_write_GBps": round(write_gbs, 1),
-                "issue": issue_summary() if (args.workload == "wbfm" and C == 256 and B == 16) else None,
-            },
+            "roofline": roofline,
             "verification": {"uncommitted_launches": counters[5], "tiles_repaired_in_place": counters[4],
                              "launches": counters[6], **r.get("verification", {"oracle_channels_checked": 0})},
             "kernel_code_tag": kernel_code_tag(),
@@ -1259,10 +1336,10 @@ def main():
             line["invalid"] = f"{counters[5]} launch(es) were not committed"
         default_headline = (world == 1 and args.workload == "wbfm" and (C, B) == (256, 16) and args.signal == "fmtone"
                             and args.quiet_fraction == 0 and not args.iqdump)
-        if world == 1 and args.workload == "wbfm" and not args.no_extras:
+        if world == 1 and args.workload == "wbfm" and args.full and not args.no_extras:
             line["end_to_end"] = end_to_end(api, device, C)
             line["single_block_latency_ms"] = single_block_latency_ms(api, device)
-        if default_headline and not args.no_extras:
+        if default_headline and args.full and not args.no_extras:
             also = also_lines(api, shard, device, args)
             if args.extras_verbose:
                 line["also"] = also
@@ -1281,7 +1358,7 @@ def main():
                 else:
                     cfg[k] = compact(d)
             line["configs"] = cfg
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         text = json.dumps(line)
         if len(text) > 8000 and not args.extras_verbose:

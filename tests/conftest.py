@@ -32,15 +32,44 @@ def oracle():
 def ref():
     """The reference's own sources compiled by oracle/Makefile (oracle/_ref).
     Built in the dev container (where /root/reference exists) and shipped
-    prebuilt to the GPU box; tests that need it skip when it is absent."""
-    from tests import reflib
+    prebuilt to the GPU box.  Where it is absent, the reference's recorded
+    answers to these same tests stand in (tests/refreplay.py); HRFD_REF_REPLAY=1
+    takes them even where oracle/_ref exists, HRFD_REF_RECORD=1 records them anew
+    (tests/golden/make_golden_ref_calls.py)."""
+    from tests import reflib, refreplay
+    if os.environ.get("HRFD_REF_REPLAY") == "1" and refreplay.have_recording():
+        yield refreplay.player(reflib.Oracle())
+        return
     if not reflib.have_ref():
         if os.path.isdir("/root/reference/radioDiags"):
             import subprocess
             subprocess.check_call(["make", "-C", reflib.ORACLE_DIR, "ref"], stdout=subprocess.DEVNULL)
+        elif refreplay.have_recording():
+            yield refreplay.player(reflib.Oracle())
+            return
         else:
             pytest.skip("oracle/_ref not built and /root/reference absent")
-    return reflib.Ref()
+    if os.environ.get("HRFD_REF_RECORD") == "1":
+        rec = refreplay.recorder(reflib.Ref(), reflib.Oracle())
+        yield rec
+        rec.save()
+        return
+    yield reflib.Ref()
+
+
+@pytest.fixture(autouse=True)
+def _ref_calls_of_this_test(request):
+    """the recorded answers of the reference are kept per test (tests/refreplay.py)"""
+    if "ref" in request.fixturenames:
+        from tests import refreplay
+        key = f"{os.path.basename(str(request.node.fspath))}::{request.node.name}"
+        if isinstance(request.getfixturevalue("ref"), refreplay.Player) and key not in refreplay.SESSION.calls:
+            pytest.skip("oracle/_ref not built, and no recorded answers of the reference for this test")
+        refreplay.SESSION.begin(key)
+        yield
+        refreplay.SESSION.finish()
+        return
+    yield
 
 
 # the behaviour-changing hooks of include/hrfd_debug.h as the Python binding spells them

@@ -57,3 +57,19 @@ def test_committed_pmc_summary_is_well_formed_and_reported_only_for_its_code(ben
     t, src = bench.pmc_traffic("wbfm_256x16")
     assert t is None and "not reported" in src
     bench._PMC = None
+
+
+def test_dump_outputs_whole_or_a_fixed_sample(bench, monkeypatch, tmp_path):
+    """--dump-outputs: a small array goes out whole in float32; a larger one as the same seeded sample from run to run"""
+    import numpy as np
+    import torch
+    small = torch.arange(-6, 6, dtype=torch.int16).reshape(3, 4)
+    got = bench.snapshot_outputs({"pcm": small, "none": None})
+    assert list(got) == ["pcm"] and got["pcm"].dtype == np.float32 and (got["pcm"] == small.numpy()).all()
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    big = torch.arange(10000, dtype=torch.int32)
+    a, b = bench.snapshot_outputs({"x": big})["x"], bench.snapshot_outputs({"x": big.clone()})["x"]
+    assert a.dtype == np.float32 and 0 < a.size <= 100 and (a == b).all()
+    assert (np.diff(a) > 0).all()                       # distinct positions, in order
+    bench.write_outputs(str(tmp_path / "out"), {"x": a})
+    assert (np.load(tmp_path / "out" / "x.npy") == a).all()

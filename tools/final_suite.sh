@@ -17,6 +17,6 @@ HRFD_LIB=$PWD/hackrfdiags_amd/lib/variants/chaos/libhrfd.so HRFD_WALK_SEEDS=40 t
 HRFD_LIB=$PWD/hackrfdiags_amd/lib/variants/chaos/libhrfd.so HRFD_WALK_SEEDS=24 timeout -k 10 900 python3 -m pytest tests/test_gpu_tx_nco.py -q -m gpu -k random_walk 2>&1 | tail -3
 echo
 echo "# bench.py --gpus 2 REHEARSED over gloo on this ONE GPU (not a measurement): the N > 1 code path of the round's bench.py"
-HRFD_BENCH_REHEARSE=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 > gpurun_out/r${ROUND:-6}_rehearsal_gloo_n2_NOT_A_MEASUREMENT.json 2> gpurun_out/r${ROUND:-6}_rehearsal.err; echo "rehearsal rc $?"; wc -c gpurun_out/r${ROUND:-6}_rehearsal_gloo_n2_NOT_A_MEASUREMENT.json
+HRFD_BENCH_REHEARSE=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 2 > $(dirname $L)/r${ROUND:-6}_rehearsal_gloo_n2_NOT_A_MEASUREMENT.json 2> $(dirname $L)/r${ROUND:-6}_rehearsal.err; echo "rehearsal rc $?"; wc -c $(dirname $L)/r${ROUND:-6}_rehearsal_gloo_n2_NOT_A_MEASUREMENT.json
 } > $L 2>&1
 cat $L

@@ -60,10 +60,9 @@ for d in sorted(glob.glob(O + "/raw_*_FETCH_SIZE")):
                     acc[k].append(float(r["Counter_Value"]))
         if not acc:
             continue
-        # HRFD_BENCH_SETTLE=0: warm-up + timed steps are all the steps the bench ran -- plus, for the receive workloads, the
-        # min(8, steps) single launches it samples behind the timed region (bench.measure_rx, round 5)
-        # (round 6: the modulator workloads sample min(4, steps) single calls behind theirs, bench.measure_mod)
-        steps_total = STEPS + WARM + (min(4, STEPS) if name.endswith(("mod_1024x16", "mod_8192x16")) else min(8, STEPS))
+        # HRFD_BENCH_SETTLE=0: warm-up + timed steps are all the steps a plain bench run makes (the single launches
+        # sampled behind the timed region belong to --full)
+        steps_total = STEPS + WARM
         tot = 0.0
         for k, v in sorted(acc.items()):
             per_step = len(v) / steps_total

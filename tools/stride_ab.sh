@@ -10,7 +10,7 @@ for rep in 1 2 3; do
     python3 - "$pad" <<'PY' >> $out
 import json, sys
 l = json.load(open("gpurun_out/_line.json"))
-print("pad", sys.argv[1], "ms_per_step", l["ms_per_step"], "kernel_ms", l["roofline"]["kernel_ms_mean"], "frac", l["roofline"]["frac"])
+print("pad", sys.argv[1], "ms_per_step", l["ms_per_step"], "kernel_ms", l["roofline"]["region_ms_per_launch"], "frac", l["roofline"]["frac"])
 PY
   done
 done
