@@ -166,6 +166,17 @@ def load() -> C.CDLL:
     L.hrfd_nco_set_frequency.argtypes = [_vp, C.c_uint32, C.c_float]
     L.hrfd_nco_reset.argtypes = [_vp, C.c_uint32]
     L.hrfd_nco_run.argtypes = [_vp, C.c_int, C.c_uint32, _vp, _vp]
+    L.hrfd_ddc_create.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]
+    L.hrfd_ddc_destroy.argtypes = [_vp]
+    L.hrfd_ddc_reset.argtypes = [_vp]
+    L.hrfd_ddc_set_tuning.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.hrfd_ddc_set_gain_shift.argtypes = [_vp, C.c_uint32, C.c_uint32]
+    L.hrfd_ddc_set_filter.argtypes = [_vp, C.c_int, _i16p, C.c_uint32]
+    L.hrfd_ddc_get_phase.argtypes = [_vp, C.c_uint32, _u32p]
+    L.hrfd_ddc_process.argtypes = [_vp, _vp, C.c_uint32, _vp]
+    L.hrfd_ddc_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp]
+    L.hrfd_ddc_receive.argtypes = [_vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
+                                   _u32p]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

@@ -506,6 +506,85 @@ class Nco:
         return (i, q) if self.n > 1 else (i[0], q[0])
 
 
+DDC_FS_OUT = 2_048_000
+DDC_STATION_SHIFT_HZ = 64_000      # the station sits 64 kHz below the channel's centre, as the reference tunes (Radio.cc:1191)
+
+
+def ddc_step(offset_hz: float, decimation: int) -> int:
+    """the DDC's phase step for a tone at offset_hz from the capture's centre: round(f / (R * 2.048e6) * 2^32) mod 2^32"""
+    return int(round(float(offset_hz) / (int(decimation) * DDC_FS_OUT) * 2.0 ** 32)) & 0xFFFFFFFF
+
+
+class Ddc:
+    """A bank of digital down-converters (hrfd_ddc_*): n_captures wideband int8 IQ captures at decimation x 2.048 MS/s
+    in, n_channels int8 IQ streams at 2.048 MS/s out, the input Rx takes."""
+
+    def __init__(self, n_captures: int, n_channels: int, decimation: int, device: int = -1):
+        self.L = _lib.load()
+        self.W, self.n, self.R = int(n_captures), int(n_channels), int(decimation)
+        h = C.c_void_p()
+        check(self.L.hrfd_ddc_create(self.W, self.n, self.R, device, C.byref(h)), "hrfd_ddc_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hrfd_ddc_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def reset(self):
+        check(self.L.hrfd_ddc_reset(self.h), "hrfd_ddc_reset")
+
+    def set_step(self, channel: int, capture: int, step: int):
+        check(self.L.hrfd_ddc_set_tuning(self.h, int(channel), int(capture), int(step) & 0xFFFFFFFF),
+              "hrfd_ddc_set_tuning")
+
+    def tune(self, channel: int, capture: int, station_offset_hz: float):
+        """put the station at station_offset_hz from the capture's centre where Rx expects it (64 kHz below the
+        channel's centre)"""
+        f = float(station_offset_hz) + DDC_STATION_SHIFT_HZ
+        if abs(f) > self.R * DDC_FS_OUT / 2:
+            raise ValueError(f"station offset {station_offset_hz} Hz + 64 kHz is outside the capture's "
+                             f"+-{self.R * DDC_FS_OUT // 2} Hz")
+        self.set_step(channel, capture, ddc_step(f, self.R))
+
+    def set_gain_shift(self, g: int, channel=ALL):
+        check(self.L.hrfd_ddc_set_gain_shift(self.h, channel, int(g)), "hrfd_ddc_set_gain_shift")
+
+    def set_filter(self, stage: int, taps):
+        """stage 0 = A (decimating), 1 = B (channel); empty taps = bypass"""
+        t = np.ascontiguousarray(taps, dtype=np.int16)
+        check(self.L.hrfd_ddc_set_filter(self.h, int(stage), t.ctypes.data_as(C.POINTER(C.c_int16)), t.size),
+              "hrfd_ddc_set_filter")
+
+    def phase(self, channel: int) -> int:
+        v = C.c_uint32(0)
+        check(self.L.hrfd_ddc_get_phase(self.h, int(channel), C.byref(v)), "hrfd_ddc_get_phase")
+        return int(v.value)
+
+    def process(self, captures: np.ndarray, out_bytes: int) -> np.ndarray:
+        """captures int8 [n_captures, decimation * out_bytes] -> int8 [n_channels, out_bytes]; blocking"""
+        cap = np.ascontiguousarray(captures, dtype=np.int8).reshape(self.W, self.R * int(out_bytes))
+        out = np.zeros((self.n, int(out_bytes)), dtype=np.int8)
+        check(self.L.hrfd_ddc_process(self.h, _ptr(cap), int(out_bytes), _ptr(out)), "hrfd_ddc_process")
+        return out
+
+    def process_device(self, d_captures, capture_stride: int, out_bytes: int, d_out, out_stride: int, stream=None):
+        """device pointers (ints); asynchronous on stream (None = the handle's own)"""
+        check(self.L.hrfd_ddc_process_device(self.h, _ptr(d_captures), int(capture_stride), int(out_bytes),
+                                             _ptr(d_out), int(out_stride), _ptr(stream)), "hrfd_ddc_process_device")
+
+    def receive(self, rx: "Rx", d_captures, capture_stride: int, block_bytes: int, n_blocks: int, d_pcm, d_n_pcm,
+                d_magnitude=None, d_allowed=None) -> int:
+        """the DDC, then rx's bank over its output (device pointers); returns the channels replayed exactly"""
+        n = C.c_uint32(0)
+        check(self.L.hrfd_ddc_receive(self.h, rx.h, _ptr(d_captures), int(capture_stride), int(block_bytes),
+                                      int(n_blocks), rx.gain_db, _ptr(d_pcm), _ptr(d_n_pcm), _ptr(d_magnitude),
+                                      _ptr(d_allowed), C.byref(n)), "hrfd_ddc_receive")
+        return int(n.value)
+
+
 class Engine:
     """Factory with the interface tests/goldencheck.py expects."""
 
@@ -534,10 +613,13 @@ class Engine:
 
 
 def q15_table(name: str) -> np.ndarray:
+    """a constant table of the library (hrfd_q15_table): the count first, then the whole table"""
     L = _lib.load()
-    buf = np.zeros(64, dtype=np.int16)
-    n = L.hrfd_q15_table(name.encode(), buf.ctypes.data_as(C.POINTER(C.c_int16)), 64)
-    return buf[:n].copy()
+    n = L.hrfd_q15_table(name.encode(), None, 0)
+    buf = np.zeros(n, dtype=np.int16)
+    if n:
+        L.hrfd_q15_table(name.encode(), buf.ctypes.data_as(C.POINTER(C.c_int16)), n)
+    return buf
 
 
 def atan2_table() -> np.ndarray:

@@ -1355,6 +1355,80 @@ static int rx_replay(hrfd_rx *h, const std::vector<uint32_t> &subset, const int8
   return HRFD_OK;
 }
 
+// The device part of hrfd_rx_process_block: d_iq [C][n_blocks][block_bytes] already on the device, PCM rows cleared;
+// returns when every channel is exact.  *n_replayed (may be NULL): channels of batch launches that failed their
+// speculation and were replayed (hrfd_ddc_receive runs the same flow on the DDC's output).
+static int rx_run_batch(hrfd_rx *h, const int8_t *d_iq, uint32_t block_bytes, uint32_t n_blocks, uint32_t gain_db,
+                        int16_t *d_pcm, uint32_t *d_npcm, uint32_t *d_mag, uint8_t *d_allowed, int8_t *d_iq256,
+                        hipStream_t s, uint32_t *n_replayed)
+{
+  const uint32_t C = h->n_channels;
+  int rc;
+  uint32_t replayed = 0;
+  const uint64_t stride = (uint64_t)block_bytes * n_blocks;
+  uint32_t viol = 0;
+  if (h->offgrid || (block_bytes % 1024u) != 0)
+  {
+    // any length: one launch of k_rx_ragged takes the whole call, block by block and exactly (rx_launch)
+    if (d_iq256 != nullptr)
+    {
+      HIP_TRY(hipMemsetAsync(d_iq256, 0, (size_t)h->n_channels * n_blocks * 2u * ((block_bytes / 2u + 7u) / 8u), s));   // (a row is filled up to the call's own count)
+    }
+    const LaunchOpts opt = {n_blocks, 0, 0, 0};
+    rc = rx_launch(h, d_iq, stride, block_bytes, n_blocks, gain_db, d_pcm, d_npcm, d_mag, d_allowed,
+                   d_iq256, s, opt);
+    if (rc != HRFD_OK) return rc;
+    if ((rc = hrfd_rx_sync(h, &viol)) != HRFD_OK) return rc;
+    if (viol != 0)
+    {
+      return fail(HRFD_ESTATE, "internal: the exact path reported %u uncommitted channel(s)", viol);
+    }
+  }
+  else
+  {
+  // Round 6: a call of more than 64 blocks runs as CHUNKS of at most 64, one batch launch each (every chunk then has the
+  // shapes a 64-block call has: the flow kernels for the FIR modes, and the gated pass on the device behind them -- until
+  // round 5 a long call with closing gates went back to the host block by block: +6 ms for 64 channels x 80 blocks).  The
+  // chunks follow each other on the stream; the host looks at every chunk's verdict before the next one starts, so a
+  // channel that did not commit is replayed over ITS chunk's blocks from the state the chunk in front left.
+  const bool batch_ok = (uint32_t)(kMaxHal + 64) * 16u <= block_bytes;
+  for (uint32_t b0 = 0; b0 < n_blocks; b0 += 64u)
+  {
+    const uint32_t nb = std::min(64u, n_blocks - b0);
+    std::vector<uint32_t> redo;                            // channels to run on the exact per-block path
+    const bool batch_ran = nb > 1 && batch_ok;
+    if (batch_ran)
+    {
+      // the chunk in one launch, blocks of a channel in parallel (speculative)
+      const LaunchOpts opt = {n_blocks, b0, 0, 0};
+      rc = rx_launch(h, d_iq + (size_t)b0 * block_bytes, stride, block_bytes, nb, gain_db, d_pcm, d_npcm,
+                     d_mag, d_allowed, d_iq256, s, opt);
+      if (rc != HRFD_OK) return rc;
+      if ((rc = hrfd_rx_sync(h, &viol)) != HRFD_OK) return rc;
+      for (uint32_t c = 0; c < C && viol != 0; c++)
+      {
+        if (h->h_fail[c] != 0) redo.push_back(c);
+      }
+      replayed += (uint32_t)redo.size();
+    }
+    else
+    {
+      for (uint32_t c = 0; c < C; c++) redo.push_back(c);
+    }
+    if ((rc = rx_replay(h, redo, d_iq, stride, block_bytes, n_blocks, gain_db, d_pcm, d_npcm, d_mag,
+                        d_allowed, d_iq256, s, !batch_ran, b0, nb)) != HRFD_OK)
+    {
+      return rc;
+    }
+  }
+  }
+  if (n_replayed != nullptr)
+  {
+    *n_replayed = replayed;
+  }
+  return HRFD_OK;
+}
+
 extern "C" int hrfd_rx_process_block(hrfd_rx *h, const int8_t *iq, uint32_t block_bytes,
                                      uint32_t n_blocks, uint32_t gain_db, int16_t *pcm,
                                      uint32_t *n_pcm, uint32_t *magnitude, uint8_t *signal_allowed,
@@ -1393,62 +1467,10 @@ extern "C" int hrfd_rx_process_block(hrfd_rx *h, const int8_t *iq, uint32_t bloc
   // mode NONE / squelched units produce no PCM: hand back zeros rather than stale bytes
   HIP_TRY(hipMemsetAsync(h->d_pcm, 0, pcm_bytes, s));
 
-  const uint64_t stride = (uint64_t)block_bytes * n_blocks;
-  int8_t *d_iq256 = iq256k_opt ? h->d_iq256 : nullptr;
-  uint32_t viol = 0;
-  if (h->offgrid || (block_bytes % 1024u) != 0)
+  if ((rc = rx_run_batch(h, h->d_iq, block_bytes, n_blocks, gain_db, h->d_pcm, h->d_npcm, h->d_mag_out, h->d_allowed,
+                         iq256k_opt ? h->d_iq256 : nullptr, s, nullptr)) != HRFD_OK)
   {
-    // any length: one launch of k_rx_ragged takes the whole call, block by block and exactly (rx_launch)
-    if (d_iq256 != nullptr)
-    {
-      HIP_TRY(hipMemsetAsync(d_iq256, 0, iq256_bytes, s));   // (a row is filled up to the call's own count)
-    }
-    const LaunchOpts opt = {n_blocks, 0, 0, 0};
-    rc = rx_launch(h, h->d_iq, stride, block_bytes, n_blocks, gain_db, h->d_pcm, h->d_npcm, h->d_mag_out, h->d_allowed,
-                   d_iq256, s, opt);
-    if (rc != HRFD_OK) return rc;
-    if ((rc = hrfd_rx_sync(h, &viol)) != HRFD_OK) return rc;
-    if (viol != 0)
-    {
-      return fail(HRFD_ESTATE, "internal: the exact path reported %u uncommitted channel(s)", viol);
-    }
-  }
-  else
-  {
-  // Round 6: a call of more than 64 blocks runs as CHUNKS of at most 64, one batch launch each (every chunk then has the
-  // shapes a 64-block call has: the flow kernels for the FIR modes, and the gated pass on the device behind them -- until
-  // round 5 a long call with closing gates went back to the host block by block: +6 ms for 64 channels x 80 blocks).  The
-  // chunks follow each other on the stream; the host looks at every chunk's verdict before the next one starts, so a
-  // channel that did not commit is replayed over ITS chunk's blocks from the state the chunk in front left.
-  const bool batch_ok = (uint32_t)(kMaxHal + 64) * 16u <= block_bytes;
-  for (uint32_t b0 = 0; b0 < n_blocks; b0 += 64u)
-  {
-    const uint32_t nb = std::min(64u, n_blocks - b0);
-    std::vector<uint32_t> redo;                            // channels to run on the exact per-block path
-    const bool batch_ran = nb > 1 && batch_ok;
-    if (batch_ran)
-    {
-      // the chunk in one launch, blocks of a channel in parallel (speculative)
-      const LaunchOpts opt = {n_blocks, b0, 0, 0};
-      rc = rx_launch(h, h->d_iq + (size_t)b0 * block_bytes, stride, block_bytes, nb, gain_db, h->d_pcm, h->d_npcm,
-                     h->d_mag_out, h->d_allowed, d_iq256, s, opt);
-      if (rc != HRFD_OK) return rc;
-      if ((rc = hrfd_rx_sync(h, &viol)) != HRFD_OK) return rc;
-      for (uint32_t c = 0; c < C && viol != 0; c++)
-      {
-        if (h->h_fail[c] != 0) redo.push_back(c);
-      }
-    }
-    else
-    {
-      for (uint32_t c = 0; c < C; c++) redo.push_back(c);
-    }
-    if ((rc = rx_replay(h, redo, h->d_iq, stride, block_bytes, n_blocks, gain_db, h->d_pcm, h->d_npcm, h->d_mag_out,
-                        h->d_allowed, d_iq256, s, !batch_ran, b0, nb)) != HRFD_OK)
-    {
-      return rc;
-    }
-  }
+    return rc;
   }
   HIP_TRY(hipMemcpyAsync(pcm, h->d_pcm, pcm_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(n_pcm, h->d_npcm, units * 4, hipMemcpyDeviceToHost, s));

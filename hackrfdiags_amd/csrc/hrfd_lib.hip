@@ -15,3 +15,4 @@
 #include "hrfd_txring.hip"
 #include "hrfd_play.hip"
 #include "hrfd_membw.hip"
+#include "hrfd_ddc.hip"

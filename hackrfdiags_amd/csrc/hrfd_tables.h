@@ -10,6 +10,8 @@
 
 #include <stdint.h>
 
+#include "hrfd_ddc_tables.h"
+
 namespace hrfd {
 
 // IqDataProcessor.cc:8-13 (front end stage 1); SsbModulator interpolator 8
@@ -154,6 +156,11 @@ static const NamedTable kNamedTables[] = {
   {"INTERP_HB2", Q_INTERP_HB2, N_INTERP_HB2},
   {"INTERP_HB1", Q_INTERP_HB1, N_INTERP_HB1},
   {"INTERPSIG_S1", Q_INTERPSIG_S1, N_INTERPSIG_S1},
+  {"DDC_COS", Q_DDC_COS, N_DDC_COS},
+  {"DDC_A2", Q_DDC_A2, N_DDC_A2},
+  {"DDC_A4", Q_DDC_A4, N_DDC_A4},
+  {"DDC_A8", Q_DDC_A8, N_DDC_A8},
+  {"DDC_B", Q_DDC_B, N_DDC_B},
 };
 
 } // namespace hrfd

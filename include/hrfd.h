@@ -353,10 +353,62 @@ int hrfd_nco_reset(hrfd_nco *h, uint32_t channel);
 int hrfd_nco_run(hrfd_nco *h, int fast, uint32_t count, float *i_out, float *q_out);
 
 /* ------------------------------------------------------------------------------
+ * DDC bank: W wideband captures -> C channel streams at 2.048 MS/s (no reference counterpart: the reference tunes one
+ * HackRF per station, 64 kHz above it, Radio.cc:1180-1191).  A capture is int8 IQ at R x 2.048 MS/s, R = 1, 2, 4, 8; a
+ * call consumes R * out_bytes bytes of every capture and produces out_bytes bytes (even, >= 2) of int8 IQ per channel,
+ * the input hrfd_rx takes.  Exact integer arithmetic, the same on every device (tests/ddc_model.py restates it):
+ *   N        absolute input-sample counter of the handle (uint64), advanced by R * out_bytes / 2 per call; every capture
+ *            keeps its last H = 255 R + 63 samples (zeros after create and reset: silence before the first call)
+ *   tuning   channel -> (capture, step, theta_ref, N_ref); sample n is mixed with theta(n) = theta_ref + (n - N_ref) step
+ *            mod 2^32 (n < N_ref too).  set_tuning at counter N: theta_ref = theta(N) under the old tuning, N_ref = N,
+ *            then the new step: the phase is continuous.  step = round(f / (R 2 048 000) 2^32) mod 2^32 moves +f to DC;
+ *            to feed hrfd_rx like the reference's radio, f = station offset + 64 000 (the station lands 64 kHz below
+ *            the channel's centre, where upconvertByFsOver4 expects it, Radio.cc:1191)
+ *   mixer    k = ((theta + 2^19) >> 20) & 4095, c = COS[k], s = COS[(k - 1024) & 4095], COS[i] = round(32767 cos(2 pi i/4096));
+ *            yI = (I c + Q s + 128) >> 8, yQ = (Q c - I s + 128) >> 8 (int16, arithmetic shifts)
+ *   stage A  a[m] = sat16((sum_k hA[k] y[m R + R - 1 - k] + 2^14) >> 15), T_A <= 64 taps; T_A = 0: a[m] = y[m R + R - 1]
+ *   stage B  b[m] = sat16((sum_k hB[k] a[m - k] + 2^14) >> 15), T_B <= 256 taps; T_B = 0: b = a
+ *   output   sat8((b + r) >> (7 - g)), r = g < 7 ? 1 << (6 - g) : 0; g = 0..7 in 6 dB steps (default 0).  A station at
+ *            -30 dBFS in the capture stays at -30 dBFS at g = 0; g gives back the bits an int8 stream would lose, and the
+ *            squelch's dBFS reading of that channel (hrfd_rx_set_threshold) moves up by 6 g dB with it.
+ * Default filters (hrfd_ddc_tables.h, tools/ddc_design.py; hrfd_q15_table "DDC_A2", "DDC_A4", "DDC_A8", "DDC_B", "DDC_COS"):
+ * stage A +-220 kHz passband, >= 60 dB from 2.048 MHz - 220 kHz (bypass at R = 1); stage B +-164 kHz, >= 60 dB beyond
+ * +-220 kHz.  Both stages refuse tap sets with sum |h| > 65535.  A call applies the filters current at its start to the
+ * capture stream, history included.  Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as
+ * well); set_tuning / get_phase work on the host's copy of N and never wait for the device: the records and taps a setter
+ * changed are copied to the device on the next call's stream, ahead of its launch.  Calls may use different streams:
+ * each launch is ordered on the device behind the handle's previous one (the per-capture history is the handle's).
+ *   hrfd_ddc_process          host buffers: captures [W][R * out_bytes] -> out [C][out_bytes]; blocking
+ *   hrfd_ddc_process_device   device buffers, rows capture_stride / out_stride bytes apart; asynchronous on `stream`
+ *                             (a hipStream_t, NULL = the handle's own)
+ *   hrfd_ddc_receive          the DDC into a buffer of the handle, [C][n_blocks * block_bytes], then the rx bank on rx's
+ *                             stream over it (rx->n_channels == C, the same device): outputs exactly those of
+ *                             hrfd_ddc_process_device followed by hrfd_rx_process_block, including the chunks of at most
+ *                             64 blocks and the exact replay of channels that failed their speculation (*n_replayed, may
+ *                             be NULL).  d_pcm [C][n_blocks][hrfd_rx_pcm_capacity(block_bytes)], d_n_pcm / d_magnitude /
+ *                             d_signal_allowed [C][n_blocks] on the device (the last two may be NULL); blocking.
+ */
+typedef struct hrfd_ddc hrfd_ddc;
+int hrfd_ddc_create(uint32_t n_captures, uint32_t n_channels, uint32_t decimation, int device, hrfd_ddc **out);
+int hrfd_ddc_destroy(hrfd_ddc *d);
+int hrfd_ddc_reset(hrfd_ddc *d);                                   /* history 0, N = 0, every theta_ref = N_ref = 0 */
+int hrfd_ddc_set_tuning(hrfd_ddc *d, uint32_t channel, uint32_t capture, uint32_t step);
+int hrfd_ddc_set_gain_shift(hrfd_ddc *d, uint32_t channel, uint32_t g);          /* HRFD_ALL_CHANNELS allowed */
+int hrfd_ddc_set_filter(hrfd_ddc *d, int stage, const int16_t *taps, uint32_t n); /* stage 0 = A, 1 = B; n = 0: bypass */
+int hrfd_ddc_get_phase(hrfd_ddc *d, uint32_t channel, uint32_t *theta);          /* theta(N) */
+int hrfd_ddc_process(hrfd_ddc *d, const int8_t *captures, uint32_t out_bytes, int8_t *out);
+int hrfd_ddc_process_device(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_stride, uint32_t out_bytes,
+                            int8_t *d_out, uint64_t out_stride, void *stream);
+int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captures, uint64_t capture_stride,
+                     uint32_t block_bytes, uint32_t n_blocks, uint32_t gain_db, int16_t *d_pcm, uint32_t *d_n_pcm,
+                     uint32_t *d_magnitude, uint8_t *d_signal_allowed, uint32_t *n_replayed);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",
- * "INTERP_HB1","INTERPSIG_S1" (Q15 taps).  Returns the tap count, 0 if unknown. */
+ * "INTERP_HB1","INTERPSIG_S1", and the DDC bank's "DDC_COS" (4096 entries), "DDC_A2","DDC_A4","DDC_A8","DDC_B" (Q15 taps).
+ * Copies min(cap, count) entries (out may be NULL to ask for the count) and returns the count, 0 if unknown. */
 int hrfd_q15_table(const char *name, int16_t *out, int cap);
 /* host-built atan2 table [256][256] (float bits) and dBFS table [257] */
 int hrfd_atan2_table(float *out);
