@@ -38,14 +38,24 @@ def mix(iq: np.ndarray, theta: np.ndarray):
     return (i * c + q * s + 128) >> 8, (q * c - i * s + 128) >> 8
 
 
-def fir_q15(h: np.ndarray, x: np.ndarray, n_out: int, first_end: int, step: int) -> np.ndarray:
-    """out[m] = sat16((sum_k h[k] x[e_m - k] + 2^14) >> 15), e_m = first_end + m * step (indices into x)"""
+def fir_acc(h: np.ndarray, x: np.ndarray, n_out: int, first_end: int, step: int) -> np.ndarray:
+    """acc[m] = sum_k h[k] x[e_m - k], e_m = first_end + m * step (indices into x)"""
     h = np.asarray(h, dtype=np.int64)
     ends = first_end + step * np.arange(n_out)
     acc = np.zeros(n_out, dtype=np.int64)
     for k in range(h.size):
         acc += h[k] * x[ends - k]
+    return acc
+
+
+def q15(acc: np.ndarray) -> np.ndarray:
+    """sat16((acc + 2^14) >> 15)"""
     return sat((acc + (1 << 14)) >> 15, 16)
+
+
+def fir_q15(h: np.ndarray, x: np.ndarray, n_out: int, first_end: int, step: int) -> np.ndarray:
+    """out[m] = sat16((sum_k h[k] x[e_m - k] + 2^14) >> 15), e_m = first_end + m * step (indices into x)"""
+    return q15(fir_acc(h, x, n_out, first_end, step))
 
 
 def default_taps(decimation: int):
@@ -98,36 +108,53 @@ class DdcModel:
         else:
             self.hB = taps
 
-    def process(self, captures: np.ndarray, out_bytes: int) -> np.ndarray:
-        """captures int8 [W, R * out_bytes] -> int8 [C, out_bytes]"""
+    def seek(self, N: int, hist: np.ndarray):
+        """move the counter to N with the H input samples in front of it (int [W, H, 2] or int8 [W, 2 H]): the
+        phase is absolute, so the next call computes what a handle that ran up to N computes"""
+        self.N = int(N)
+        self.hist = np.asarray(hist).reshape(self.W, self.H, 2).astype(np.int64)
+
+    def process(self, captures: np.ndarray, out_bytes: int, stages: bool = False):
+        """captures int8 [W, R * out_bytes] -> int8 [C, out_bytes]; stages=True also returns a dict of int64
+        [C, 2, n] arrays (rail 0 = I, 1 = Q): "accA" stage A's sums sum_k hA[k] y[..] (before rounding and sat16),
+        "a" a16, both for the a16 indices -255 .. M - 1 of the call (stage B's look-back first; with T_A = 0 "accA"
+        is None), "accB" stage B's sums (None with T_B = 0) and "b" b16 for the call's M outputs"""
         R, H, M = self.R, self.H, out_bytes // 2
         cap = np.asarray(captures, dtype=np.int8).reshape(self.W, R * M, 2).astype(np.int64)
         stream = np.concatenate([self.hist, cap], axis=1)           # [W, H + R M, 2]: index H + j = local sample j
         out = np.zeros((self.C, M, 2), dtype=np.int64)
         n_abs = self.N - H + np.arange(H + R * M, dtype=np.int64)     # absolute sample index of every stream entry
+        st = {"accA": None if self.hA.size == 0 else np.zeros((self.C, 2, M + 255), dtype=np.int64),
+              "a": np.zeros((self.C, 2, M + 255), dtype=np.int64),
+              "accB": None if self.hB.size == 0 else np.zeros((self.C, 2, M), dtype=np.int64),
+              "b": np.zeros((self.C, 2, M), dtype=np.int64)}
         for c in range(self.C):
             theta = (int(self.theta_ref[c]) + (n_abs - int(self.n_ref[c])) * int(self.step[c])) & MASK32
-            yi, yq = mix(stream[int(self.capture[c])], theta)
+            y = mix(stream[int(self.capture[c])], theta)
             # stage A: a[m] = sum_k hA[k] y[m R + R - 1 - k]; entries of the stream before 0 are never reached
-            if self.hA.size == 0:
-                ai, aq = yi[H + R - 1 - 255 * R::R][:M + 255], yq[H + R - 1 - 255 * R::R][:M + 255]
-            else:
-                first = H + R - 1 - 255 * R                            # a16 index -255 (stage B's deepest look-back)
-                ai = fir_q15(self.hA, yi, M + 255, first, R)
-                aq = fir_q15(self.hA, yq, M + 255, first, R)
-            # stage B at 2.048 MS/s; a16 index m lives at position m + 255
-            if self.hB.size == 0:
-                bi, bq = ai[255:], aq[255:]
-            else:
-                bi = fir_q15(self.hB, ai, M, 255, 1)
-                bq = fir_q15(self.hB, aq, M, 255, 1)
-            g = int(self.g[c])
-            r = (1 << (6 - g)) if g < 7 else 0
-            out[c, :, 0] = sat((bi + r) >> (7 - g), 8)
-            out[c, :, 1] = sat((bq + r) >> (7 - g), 8)
+            first = H + R - 1 - 255 * R                                # a16 index -255 (stage B's deepest look-back)
+            for rail in range(2):
+                if self.hA.size == 0:
+                    a = y[rail][first::R][:M + 255]
+                else:
+                    acc = fir_acc(self.hA, y[rail], M + 255, first, R)
+                    a = q15(acc)
+                    st["accA"][c, rail] = acc
+                # stage B at 2.048 MS/s; a16 index m lives at position m + 255
+                if self.hB.size == 0:
+                    b = a[255:]
+                else:
+                    acc = fir_acc(self.hB, a, M, 255, 1)
+                    b = q15(acc)
+                    st["accB"][c, rail] = acc
+                st["a"][c, rail], st["b"][c, rail] = a, b
+                g = int(self.g[c])
+                r = (1 << (6 - g)) if g < 7 else 0
+                out[c, :, rail] = sat((b + r) >> (7 - g), 8)
         self.hist = stream[:, -H:].copy()
         self.N += R * M
-        return out.reshape(self.C, 2 * M).astype(np.int8)
+        out = out.reshape(self.C, 2 * M).astype(np.int8)
+        return (out, st) if stages else out
 
 
 # ---- the selectivity scenario (tests/test_ddc_model.py on the model, tests/test_gpu_ddc.py on the device)

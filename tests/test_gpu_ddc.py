@@ -91,12 +91,18 @@ def test_random_taps_and_every_gain_bit_exact(R):
 
 
 # 2. streaming
-def test_streaming_calls_retune_filter_change_capture_switch_reset():
-    R, W, C = 4, 2, 3
+# tile remainders: M in {1 .. 5, 255 .. 257, 511 .. 513, 1023 .. 1025, 2047, 2049, 4095, 4097} outputs, one stream of
+# calls per R (history and phase cross every shape; the sizes cover tiles of 256, 512, 1024 or 2048 outputs)
+TILE_SEQ = [2 * M for M in (1, 2, 3, 4, 5, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2049, 4095, 4097)]
+STREAM_CASES = [(4, [2, 510, 1000, 1026, 262144, 3074, 2])] + [(R, TILE_SEQ) for R in (1, 2, 4, 8)]
+
+
+@pytest.mark.parametrize("R,seq", STREAM_CASES, ids=["r4_mixed", "r1_tiles", "r2_tiles", "r4_tiles", "r8_tiles"])
+def test_streaming_calls_retune_filter_change_capture_switch_reset(R, seq):
+    W, C = 2, 3
     d, m = both(W, C, R)
     for c in range(C):
         tune_both(d, m, c, c % W, dm.ddc_step(100_000 * (c + 1) - 150_000, R))
-    seq = [2, 510, 1000, 1026, 262144, 3074, 2]
     for i, ob in enumerate(seq):
         if i == 2:
             tune_both(d, m, 1, 1, dm.ddc_step(-777_000, R))       # retune
@@ -117,78 +123,128 @@ def test_streaming_calls_retune_filter_change_capture_switch_reset():
 
 
 # 3. strides, and calls on different streams
-def test_padded_strides_leave_guard_bytes(torch_dev):
-    """padded capture / output strides, an odd output address; the calls alternate between a stream of the caller and
-    the handle's own without waiting in between (the handle orders them on the device)"""
+def _legacy_layout(R, ob, k):
+    """capture offset, capture stride, output offset, output stride of call k"""
+    return 0, R * ob + 1234, 3, ob + 77 * 2 + 6
+
+
+def _sweep_layout(R, ob, k):
+    """over the 8 calls: capture base offsets 0, 2, .. 14 bytes, capture strides at every even residue mod 16, output
+    base offsets 0 .. 7, odd and even output strides (ob is a multiple of 16)"""
+    return 2 * k, R * ob + 16 + 2 * ((5 * k) % 8), (3 * k) % 8, ob + 8 + (k % 2)
+
+
+STRIDE_CASES = [(2, 5000, 3, _legacy_layout)] + [(R, 3008, 8, _sweep_layout) for R in (1, 2, 4, 8)]
+
+
+@pytest.mark.parametrize("R,ob,n_calls,layout", STRIDE_CASES,
+                         ids=["r2_odd_output", "r1_alignment", "r2_alignment", "r4_alignment", "r8_alignment"])
+def test_padded_strides_leave_guard_bytes(torch_dev, R, ob, n_calls, layout):
+    """padded capture / output strides, unaligned capture and output addresses; the calls alternate between a stream
+    of the caller and the handle's own without waiting in between (the handle orders them on the device).  Guard bytes
+    before, between and after the output rows stay; the captures stay unchanged"""
     torch, dev = torch_dev
-    R, W, C, ob = 2, 2, 5, 5000
+    W, C = 2, 5
     d, m = both(W, C, R)
     for c in range(C):
         tune_both(d, m, c, (c + 1) % W, dm.ddc_step(-300_000 + 90_000 * c, R))
-    cs, os_ = R * ob + 1234, ob + 77 * 2 + 6
-    n_calls = 3
     caps = [lcg_captures(W, R * ob, 5 + k) for k in range(n_calls)]
-    dcap = torch.zeros((n_calls, W, cs), dtype=torch.int8, device=dev)
+    lay = [layout(R, ob, k) for k in range(n_calls)]
+    dcaps, douts, ref_caps = [], [], []
     for k in range(n_calls):
-        dcap[k, :, :R * ob] = torch.from_numpy(caps[k]).to(dev)
-    douts = [torch.full((C + 1, os_), 0x5A, dtype=torch.int8, device=dev) for _ in range(n_calls)]
+        co, cs, oo, os_ = lay[k]
+        host = np.full(co + W * cs + 16, 0x33, dtype=np.int8)
+        for w in range(W):
+            host[co + w * cs:co + w * cs + R * ob] = caps[k][w]
+        ref_caps.append(host)
+        dcaps.append(torch.from_numpy(host).to(dev))
+        douts.append(torch.full((oo + C * os_ + 16,), 0x5A, dtype=torch.int8, device=dev))
     side = torch.cuda.Stream()
     torch.cuda.synchronize()
     for k in range(n_calls):
+        co, cs, oo, os_ = lay[k]
         stream = side.cuda_stream if k % 2 == 0 else None
-        d.process_device(dcap[k].data_ptr(), cs, ob, douts[k].data_ptr() + 3, os_, stream)
+        d.process_device(dcaps[k].data_ptr() + co, cs, ob, douts[k].data_ptr() + oo, os_, stream)
     torch.cuda.synchronize()
     for k in range(n_calls):
+        co, cs, oo, os_ = lay[k]
         want = m.process(caps[k], ob)
-        host = douts[k].cpu().numpy().reshape(-1)
+        host = douts[k].cpu().numpy()
         for c in range(C):
-            row = host[3 + c * os_:3 + c * os_ + ob]
+            row = host[oo + c * os_:oo + c * os_ + ob]
             assert (row == want[c]).all(), f"call {k} ch{c}"
-            guard = host[3 + c * os_ + ob:3 + (c + 1) * os_]
-            assert (guard == 0x5A).all(), f"guard bytes of ch{c} touched"
-        assert (host[:3] == 0x5A).all() and (host[3 + C * os_:] == 0x5A).all()
+            guard = host[oo + c * os_ + ob:oo + (c + 1) * os_]
+            assert (guard == 0x5A).all(), f"call {k}: guard bytes behind ch{c} touched"
+        assert (host[:oo] == 0x5A).all() and (host[oo + C * os_:] == 0x5A).all(), f"call {k}: guard bytes touched"
+        assert (dcaps[k].cpu().numpy() == ref_caps[k]).all(), f"call {k}: the captures changed"
 
 
 # 4. receive against model + oracle
-def _receive_case(torch, dev, oracle, mode, R, block_bytes, n_blocks, threshold=None, level_drop=False, seed=0):
+def _receive_case(torch, dev, oracle, mode, R, block_bytes, n_blocks, threshold=None, level_drop=False, seed=0,
+                  calls=None, gain_db=0, mode_gain=None, squelch_outputs=True):
+    """hrfd_ddc_receive over `calls` ([(block_bytes, n_blocks)], default one call) on one (Ddc, Rx) pair against the
+    model followed by the CPU oracle's rx chain, block by block, state carried across the calls on both sides.
+    squelch_outputs=False passes d_magnitude / d_allowed as NULL (the PCM and its counts are still checked)."""
     W, C = 2, 4
+    calls = calls or [(block_bytes, n_blocks)]
     d, m = both(W, C, R)
     rx = api.Rx(C, device=0)
     rx.set_mode(mode)
     if threshold is not None:
         rx.set_threshold(threshold)
+    if mode_gain is not None:
+        rx.set_gain(mode, mode_gain)
+    rx.gain_db = gain_db
     offs = [-400_000, 150_000, 0, 320_000]
     for c in range(C):
         tune_both(d, m, c, c % W, dm.ddc_step(offs[c] + 64_000, R))
         d.set_gain_shift(2, c)
         m.set_gain_shift(c, 2)
-    ob = block_bytes * n_blocks
-    cap = lcg_captures(W, R * ob, seed).astype(np.int16)
-    cap = (cap // 6).astype(np.int8)                             # a noise floor the rx chain can demodulate
-    if level_drop:
-        cap[:, R * ob // 3:] = (cap[:, R * ob // 3:] // 16).astype(np.int8)   # gates close mid-batch
-    dcap = torch.from_numpy(cap).to(dev)
-    npcm_cap = api.pcm_capacity(block_bytes)
-    d_pcm = torch.zeros((C, n_blocks, npcm_cap), dtype=torch.int16, device=dev)
-    d_n = torch.zeros((C, n_blocks), dtype=torch.int32, device=dev)
-    d_mag = torch.zeros((C, n_blocks), dtype=torch.int32, device=dev)
-    d_al = torch.zeros((C, n_blocks), dtype=torch.uint8, device=dev)
-    torch.cuda.synchronize()
-    replayed = d.receive(rx, dcap.data_ptr(), R * ob, block_bytes, n_blocks, d_pcm.data_ptr(), d_n.data_ptr(),
-                         d_mag.data_ptr(), d_al.data_ptr())
-    streams = m.process(cap, ob)
-    pcm, n, mag, al = (t.cpu().numpy() for t in (d_pcm, d_n, d_mag, d_al))
+    orcs = []
     for c in range(C):
         o = oracle.rx()
         o.set_mode(mode)
         if threshold is not None:
             o.set_threshold(threshold)
-        for b in range(n_blocks):
-            p, mg, allowed, _ = o.process(streams[c, b * block_bytes:(b + 1) * block_bytes])
-            assert int(n[c, b]) == p.size, f"{mode} ch{c} blk{b} n_pcm"
-            assert (pcm[c, b, :p.size] == p).all(), f"{mode} ch{c} blk{b} pcm"
-            assert int(mag[c, b]) == mg and bool(al[c, b]) == allowed, f"{mode} ch{c} blk{b} squelch"
-    return al, replayed, rx.debug_counters()
+        if mode_gain is not None:
+            o.set_gain(mode, mode_gain)
+        o.gain_db = gain_db
+        orcs.append(o)
+    total = sum(bb * nb for bb, nb in calls)
+    cap_all = lcg_captures(W, R * total, seed).astype(np.int16)
+    cap_all = (cap_all // 6).astype(np.int8)                     # a noise floor the rx chain can demodulate
+    if level_drop:
+        cap_all[:, R * total // 3:] = (cap_all[:, R * total // 3:] // 16).astype(np.int8)   # gates close mid-batch
+    als, replayed = [], 0
+    pos = 0
+    for call, (bb, nb) in enumerate(calls):
+        ob = bb * nb
+        cap = np.ascontiguousarray(cap_all[:, R * pos:R * (pos + ob)])
+        pos += ob
+        dcap = torch.from_numpy(cap).to(dev)
+        npcm_cap = api.pcm_capacity(bb)
+        d_pcm = torch.zeros((C, nb, npcm_cap), dtype=torch.int16, device=dev)
+        d_n = torch.zeros((C, nb), dtype=torch.int32, device=dev)
+        d_mag = torch.zeros((C, nb), dtype=torch.int32, device=dev)
+        d_al = torch.zeros((C, nb), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        replayed += d.receive(rx, dcap.data_ptr(), R * ob, bb, nb, d_pcm.data_ptr(), d_n.data_ptr(),
+                              d_mag.data_ptr() if squelch_outputs else None, d_al.data_ptr() if squelch_outputs else None)
+        streams = m.process(cap, ob)
+        pcm, n, mag, al = (t.cpu().numpy() for t in (d_pcm, d_n, d_mag, d_al))
+        oal = np.zeros((C, nb), dtype=bool)
+        for c in range(C):
+            for b in range(nb):
+                p, mg, allowed, _ = orcs[c].process(streams[c, b * bb:(b + 1) * bb])
+                oal[c, b] = allowed
+                assert int(n[c, b]) == p.size, f"{mode} call {call} ch{c} blk{b} n_pcm"
+                assert (pcm[c, b, :p.size] == p).all(), f"{mode} call {call} ch{c} blk{b} pcm"
+                if squelch_outputs:
+                    assert int(mag[c, b]) == mg and bool(al[c, b]) == allowed, f"{mode} call {call} ch{c} blk{b} squelch"
+        if not squelch_outputs:
+            assert not mag.any() and not al.any(), "NULL squelch outputs: the caller's rows must stay untouched"
+        als.append(al if squelch_outputs else oal)
+    return np.concatenate(als, axis=1), replayed, rx.debug_counters()
 
 
 # 32768-byte blocks: long enough for the rx bank's speculative batch launch (hrfd_rx_process_block takes blocks of at
@@ -212,6 +268,32 @@ def test_receive_with_closing_gates(torch_dev, oracle, mode, n_blocks):
     assert al[:, 0].all() and not al[:, -1].any(), "the scenario must open and then close the gates"
     repairs = counters[4]                       # device repairs over the handle's life (hrfd_rx_debug_counters)
     assert replayed + repairs > 0, f"no repair ran (n_replayed {replayed}, counters {counters})"
+
+
+# hrfd_ddc_receive beyond one call: consecutive calls on one pair, block lengths off the 1024-byte grid (k_rx_ragged),
+# off the 512-byte grid (the handle stays off it), below the batch threshold (the exact per-block path), the smallest
+# batched length, gains, and the squelch outputs passed as NULL
+RECEIVE_CASES = {
+    "three_calls": dict(mode=WBFM, R=4, calls=[(BATCH_BLOCK, 2)] * 3),
+    "ragged_261632": dict(mode=FM, R=2, calls=[(261632, 2)]),
+    "ragged_16896": dict(mode=AM, R=8, calls=[(16896, 3), (16896, 2)]),
+    "offgrid_1000": dict(mode=LSB, R=2, calls=[(FULL, 1), (1000, 3), (FULL, 1)]),
+    "exact_20480": dict(mode=USB, R=4, calls=[(20480, 3), (20480, 2)]),
+    "batched_21504_gains": dict(mode=WBFM, R=2, calls=[(21504, 3), (21504, 4)], gain_db=20, mode_gain=4000.0),
+    "fm_mode_gain": dict(mode=FM, R=1, calls=[(21504, 3)], gain_db=6, mode_gain=4321.0),
+    "null_squelch_outputs": dict(mode=FM, R=4, calls=[(BATCH_BLOCK, 3), (BATCH_BLOCK, 2)], threshold=-30,
+                                 level_drop=True, squelch_outputs=False),
+}
+
+
+@pytest.mark.parametrize("case", list(RECEIVE_CASES), ids=list(RECEIVE_CASES))
+def test_receive_beyond_one_call(torch_dev, oracle, case):
+    torch, dev = torch_dev
+    kw = dict(RECEIVE_CASES[case])
+    mode, R = kw.pop("mode"), kw.pop("R")
+    al, _, _ = _receive_case(torch, dev, oracle, mode, R, 0, 0, seed=31 + len(case), **kw)
+    if case == "null_squelch_outputs":
+        assert al[:, 0].all() and not al[:, -1].any(), "the squelch must open and close in this scenario"
 
 
 # 5. size

@@ -37,6 +37,8 @@ GROUPS = [
     ("shim_classes", "test_shim", "", 5),
     ("modulators_nco", "test_gpu_tx_nco", "", 25),
     ("receive_everything_else", "test_gpu_rx", "", 120),
+    ("ddc_bank", "test_gpu_ddc", "", 36),
+    ("ddc_edges", "test_gpu_ddc_edges", "", 36),
 ]
 
 
