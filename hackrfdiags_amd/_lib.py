@@ -177,6 +177,19 @@ def load() -> C.CDLL:
     L.hrfd_ddc_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp]
     L.hrfd_ddc_receive.argtypes = [_vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
                                    _u32p]
+    if hasattr(L, "hrfd_duc_create"):                      # (an older build named by HRFD_LIB has no DUC bank)
+        L.hrfd_duc_create.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_duc_destroy.argtypes = [_vp]
+        L.hrfd_duc_reset.argtypes = [_vp]
+        L.hrfd_duc_set_tuning.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.hrfd_duc_set_amplitude.argtypes = [_vp, C.c_uint32, C.c_uint32]
+        L.hrfd_duc_set_output_shift.argtypes = [_vp, C.c_uint32, C.c_uint32]
+        L.hrfd_duc_set_filter.argtypes = [_vp, C.c_int, _i16p, C.c_uint32]
+        L.hrfd_duc_get_phase.argtypes = [_vp, C.c_uint32, _u32p]
+        L.hrfd_duc_get_clips.argtypes = [_vp, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.hrfd_duc_process.argtypes = [_vp, _vp, C.c_uint32, _vp]
+        L.hrfd_duc_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp]
+        L.hrfd_duc_transmit.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

@@ -585,6 +585,87 @@ class Ddc:
         return int(n.value)
 
 
+def duc_step(offset_hz: float, interpolation: int) -> int:
+    """the DUC's phase step that puts a channel's DC at offset_hz from the capture's centre (the same formula as
+    ddc_step): round(f / (R * 2.048e6) * 2^32) mod 2^32"""
+    return ddc_step(offset_hz, interpolation)
+
+
+class Duc:
+    """A bank of digital up-converters (hrfd_duc_*): n_channels int8 IQ streams at 2.048 MS/s (what Mod writes) in,
+    n_captures wideband int8 IQ captures at interpolation x 2.048 MS/s out, each the sum of the channels tuned to it."""
+
+    def __init__(self, n_captures: int, n_channels: int, interpolation: int, device: int = -1):
+        self.L = _lib.load()
+        self.W, self.n, self.R = int(n_captures), int(n_channels), int(interpolation)
+        h = C.c_void_p()
+        check(self.L.hrfd_duc_create(self.W, self.n, self.R, device, C.byref(h)), "hrfd_duc_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hrfd_duc_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def reset(self):
+        check(self.L.hrfd_duc_reset(self.h), "hrfd_duc_reset")
+
+    def set_step(self, channel: int, capture: int, step: int):
+        check(self.L.hrfd_duc_set_tuning(self.h, int(channel), int(capture), int(step) & 0xFFFFFFFF),
+              "hrfd_duc_set_tuning")
+
+    def tune(self, channel: int, capture: int, offset_hz: float):
+        """put the channel's DC (the station, as the modulators write it) at offset_hz from the capture's centre"""
+        if abs(float(offset_hz)) > self.R * DDC_FS_OUT / 2:
+            raise ValueError(f"offset {offset_hz} Hz is outside the capture's +-{self.R * DDC_FS_OUT // 2} Hz")
+        self.set_step(channel, capture, duc_step(offset_hz, self.R))
+
+    def set_amplitude(self, amplitude: int, channel=ALL):
+        """A = 0..32768 (32768: unity, 0: muted)"""
+        check(self.L.hrfd_duc_set_amplitude(self.h, channel, int(amplitude)), "hrfd_duc_set_amplitude")
+
+    def set_output_shift(self, s: int, capture=ALL):
+        check(self.L.hrfd_duc_set_output_shift(self.h, capture, int(s)), "hrfd_duc_set_output_shift")
+
+    def set_filter(self, stage: int, taps):
+        """stage 0 = A (interpolating), 1 = B (channel); empty taps = bypass"""
+        t = np.ascontiguousarray(taps, dtype=np.int16)
+        check(self.L.hrfd_duc_set_filter(self.h, int(stage), t.ctypes.data_as(C.POINTER(C.c_int16)), t.size),
+              "hrfd_duc_set_filter")
+
+    def phase(self, channel: int) -> int:
+        v = C.c_uint32(0)
+        check(self.L.hrfd_duc_get_phase(self.h, int(channel), C.byref(v)), "hrfd_duc_get_phase")
+        return int(v.value)
+
+    def clips(self, capture: int) -> int:
+        """output samples (I and Q apart) of the capture that saturated since create / reset; waits for the last call"""
+        v = C.c_uint64(0)
+        check(self.L.hrfd_duc_get_clips(self.h, int(capture), C.byref(v)), "hrfd_duc_get_clips")
+        return int(v.value)
+
+    def process(self, channels: np.ndarray, in_bytes: int) -> np.ndarray:
+        """channels int8 [n_channels, in_bytes] -> int8 [n_captures, interpolation * in_bytes]; blocking"""
+        x = np.ascontiguousarray(channels, dtype=np.int8).reshape(self.n, int(in_bytes))
+        out = np.zeros((self.W, self.R * int(in_bytes)), dtype=np.int8)
+        check(self.L.hrfd_duc_process(self.h, _ptr(x), int(in_bytes), _ptr(out)), "hrfd_duc_process")
+        return out
+
+    def process_device(self, d_channels, channel_stride: int, in_bytes: int, d_captures, capture_stride: int,
+                       stream=None):
+        """device pointers (ints); asynchronous on stream (None = the handle's own)"""
+        check(self.L.hrfd_duc_process_device(self.h, _ptr(d_channels), int(channel_stride), int(in_bytes),
+                                             _ptr(d_captures), int(capture_stride), _ptr(stream)),
+              "hrfd_duc_process_device")
+
+    def transmit(self, mod: "Mod", d_pcm, n_per_channel: int, d_captures, capture_stride: int, stream=None):
+        """mod's bank over d_pcm, then the DUC over its output (device pointers); asynchronous on stream"""
+        check(self.L.hrfd_duc_transmit(self.h, mod.h, _ptr(d_pcm), int(n_per_channel), _ptr(d_captures),
+                                       int(capture_stride), _ptr(stream)), "hrfd_duc_transmit")
+
+
 class Engine:
     """Factory with the interface tests/goldencheck.py expects."""
 

@@ -1,0 +1,905 @@
+// hackrfdiags_amd/csrc/hrfd_duc.hip -- hrfd_duc_*: a bank of digital up-converters behind hrfd_mod.
+//
+// C channel streams of int8 IQ at 2.048 MS/s in, W wideband int8 IQ captures at R x 2.048 MS/s out: per channel stage B
+// (channel FIR at 2.048 MS/s), an amplitude, stage A (zero-stuffed interpolation by R) and a mixer (e^{+j theta(n)} from
+// the DDC's 4096-entry Q15 cosine table); the channels of a capture are summed in int32 and shifted to int8.  Exact
+// integer arithmetic, contract in include/hrfd.h; tests/duc_model.py restates it in numpy.
+//
+// One workgroup (256 threads) per (capture, tile of kDucTile channel samples = R kDucTile wideband outputs); it loops over
+// the channels mapped to its capture (a per-capture list on the device) and keeps the sums in registers:
+//   1. the tile's channel samples plus the look-back of both filters are read as dwords into two int16 rails u = x << 8
+//   2. stage B (4 consecutive outputs per lane, ddc_fir's register-blocked v_dot2_i32_i16) and the amplitude write v
+//   3. every lane owns two pairs of neighbouring channel positions (2 tid, 2 tid + 1 and 512 more): one window of v per
+//      pair gives both positions' R polyphase outputs (taps.x for the even position, taps.y -- one leading zero -- for the
+//      odd one), so no multiply touches a stuffed zero; neighbouring lanes read neighbouring dwords.  The 2 R wideband
+//      outputs of a pair are mixed and added to the lane's int32 sums.
+// After the last channel: one rounded, saturated int8 store per output and one clip count per workgroup (a wave
+// reduction, an LDS counter, one global atomicAdd).  C extra workgroups per launch copy the last H samples of every
+// channel into the other history buffer (ping-pong: the tiles of the same launch read the current one).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <mutex>
+#include <vector>
+
+#include "hrfd_duc_tables.h"
+
+namespace hrfd {
+
+constexpr int kDucTile = 1024;             // channel samples per workgroup
+constexpr int kDucThreads = 256;
+constexpr int kDucMaxTA = 64;
+constexpr int kDucMaxTB = 256;
+constexpr int kDucH = 318;                 // history: stage B's 255 samples behind stage A's 63 (R = 1)
+constexpr int kDucJB = kDucMaxTB / 2 + 1;  // packed tap dwords of stage B
+constexpr int kDucJA = 40;                 // R branches x ((63 / R + 1) / 2 + 1) packed tap dwords at most (R = 8: 8 x 5)
+constexpr uint32_t kDucMaxChannels = 32768;
+constexpr uint32_t kDucMaxShift = 24;
+// u rails: local samples [0, OFF + kDucTile + 16), OFF <= 318 (look-back of both stages, even)
+constexpr int kDucUDw = (kDucH + kDucTile + 16) / 2 + 8;
+// v rails: kDucTile + LA (<= 63) samples rounded up to quads, plus the last window's overrun
+constexpr int kDucVDw = (kDucTile + 64 + 8) / 2 + 8;
+
+struct DucChanDev
+{
+  uint32_t capture;
+  uint32_t step;
+  uint32_t theta_ref;
+  uint32_t amp;
+  uint64_t n_ref;
+};
+
+struct DucParams
+{
+  const int8_t *in;            // [C] rows of 2M bytes, in_stride apart
+  uint64_t in_stride;
+  const int8_t *hist_in;       // [C][kDucH] IQ samples: the samples in front of this call
+  int8_t *hist_out;            // [C][kDucH]: the samples in front of the next call
+  int8_t *cap;                 // [W] rows of 2 R M bytes, cap_stride apart
+  uint64_t cap_stride;
+  const DucChanDev *chan;
+  const uint32_t *list_off;    // [W + 1]: the channels of capture w are list[list_off[w] .. list_off[w + 1])
+  const uint32_t *list;        // [C]
+  const uint32_t *shift;       // [W] output shifts
+  const uint2 *taps;           // [kDucJA] stage A: branch p at p * JA, then [kDucJB] stage B
+  const uint32_t *cs;          // [4096] (COS[k], COS[(k - 1024) & 4095]) as packed int16
+  unsigned long long *clips;   // [W]
+  uint64_t n0;                 // absolute index of the call's first wideband output
+  uint32_t M;                  // channel samples per channel
+  uint32_t n_tiles;
+  uint32_t n_channels;
+  uint32_t n_captures;
+  int TA, TB;                  // 0 = bypass
+  int LA;                      // stage A look-back in channel samples: (TA - 1) / R
+  int JA, JB;                  // packed tap dwords in use (JA per branch)
+};
+
+// one IQ sample of channel c at call-local index j (history in front of the call, zeros beyond it) as (I, Q) bytes
+__device__ __forceinline__ uint32_t duc_load_sample(const DucParams &P, uint32_t c, int64_t j)
+{
+  if (j >= 0 && j < (int64_t)P.M)
+  {
+    return *(const uint16_t *)(P.in + (uint64_t)c * P.in_stride + 2 * (uint64_t)j);
+  }
+  if (j < 0 && j >= -(int64_t)kDucH)
+  {
+    return *(const uint16_t *)(P.hist_in + ((uint64_t)c * kDucH + (uint64_t)(kDucH + j)) * 2);
+  }
+  return 0u;
+}
+
+// samples j, j + 1 (j even) as (I0, Q0, I1, Q1) bytes: one dword load where both lie in one aligned source dword
+__device__ __forceinline__ uint32_t duc_load_pair(const DucParams &P, uint32_t c, int64_t j)
+{
+  if (j >= 0 && j + 1 < (int64_t)P.M)
+  {
+    const int8_t *p = P.in + (uint64_t)c * P.in_stride + 2 * (uint64_t)j;
+    if (((uintptr_t)p & 3u) == 0)
+    {
+      return *(const uint32_t *)p;
+    }
+  }
+  else if (j < 0 && j >= -(int64_t)kDucH)
+  {
+    // a history row is kDucH = 318 samples = 636 bytes (4-byte aligned) and j is even
+    return *(const uint32_t *)(P.hist_in + ((uint64_t)c * kDucH + (uint64_t)(kDucH + j)) * 2);
+  }
+  return duc_load_sample(P, c, j) | (duc_load_sample(P, c, j + 1) << 16);
+}
+
+__device__ __forceinline__ uint32_t pack16(int lo, int hi) { return ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16); }
+
+template <int R>
+__global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
+{
+  __shared__ uint32_t cs[4096];
+  __shared__ uint32_t uI[kDucUDw], uQ[kDucUDw];
+  __shared__ uint32_t vI[kDucVDw], vQ[kDucVDw];
+  __shared__ uint2 taps[kDucJA + kDucJB];
+  __shared__ uint32_t clip_sum;
+  const int tid = threadIdx.x;
+  const uint32_t n_units = P.n_tiles * P.n_captures;
+  if (blockIdx.x >= n_units)
+  {
+    // history: the last kDucH samples of (history, this call's input) of channel c, for the next call
+    const uint32_t c = blockIdx.x - n_units;
+    for (int i = tid; i < kDucH; i += kDucThreads)
+    {
+      const uint32_t v = duc_load_sample(P, c, (int64_t)P.M - kDucH + i);
+      *(uint16_t *)(P.hist_out + ((uint64_t)c * kDucH + i) * 2) = (uint16_t)v;
+    }
+    return;
+  }
+  const uint32_t w = blockIdx.x / P.n_tiles;
+  const int m_t = (int)(blockIdx.x - w * P.n_tiles) * kDucTile;
+  const int cnt = min(kDucTile, (int)P.M - m_t);
+
+  for (int i = tid; i < 4096; i += kDucThreads)
+  {
+    cs[i] = P.cs[i];
+  }
+  for (int i = tid; i < kDucJA + kDucJB; i += kDucThreads)
+  {
+    taps[i] = P.taps[i];
+  }
+  if (tid == 0)
+  {
+    clip_sum = 0u;
+  }
+  const int TA = P.TA, TB = P.TB, LA = P.LA;
+  const int LB = TB > 0 ? TB - 1 : 0;
+  const int OFF = (LA + LB + 1) & ~1;                   // u local index 0 = channel position m_t - OFF (even)
+  const int delta = OFF - LA - LB;                      // stage B window of v index k starts at u index k + delta
+  const int nud = (OFF + kDucTile + 16) / 2;            // u dwords filled
+  const int nq = (kDucTile + LA + 3) / 4;               // v quads: v index k = channel position m_t - LA + k
+
+  int sI[2][2 * R], sQ[2][2 * R];
+#pragma unroll
+  for (int h = 0; h < 2; h++)
+  {
+#pragma unroll
+    for (int i = 0; i < 2 * R; i++)
+    {
+      sI[h][i] = 0;
+      sQ[h][i] = 0;
+    }
+  }
+
+  const uint32_t c_end = P.list_off[w + 1];
+  for (uint32_t ci = P.list_off[w]; ci < c_end; ci++)
+  {
+    const uint32_t c = P.list[ci];
+    const DucChanDev ch = P.chan[c];
+    if (ch.amp == 0u)
+    {
+      continue;                                         // muted: every y is 0 (uniform over the workgroup)
+    }
+    // 1. u rails: dword p holds samples m_t - OFF + 2p, + 1 (x << 8 in every half)
+    for (int p = tid; p < nud; p += kDucThreads)
+    {
+      const uint32_t d = duc_load_pair(P, c, (int64_t)m_t - OFF + 2 * p);
+      uI[p] = (d & 0x00ff00ffu) << 8;
+      uQ[p] = d & 0xff00ff00u;
+    }
+    __syncthreads();
+
+    // 2. stage B and the amplitude: v index 4q + i
+    const int amp = (int)ch.amp;
+    for (int q = tid; q < nq; q += kDucThreads)
+    {
+      int bI[4], bQ[4];
+      const int s0 = 4 * q + delta;
+      if (TB == 0)
+      {
+        const int16_t *u16I = (const int16_t *)uI, *u16Q = (const int16_t *)uQ;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+        {
+          bI[i] = u16I[s0 + i];
+          bQ[i] = u16Q[s0 + i];
+        }
+      }
+      else
+      {
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+        {
+          bI[i] = 1 << 14;
+          bQ[i] = 1 << 14;
+        }
+        ddc_fir_any<4, 1>(s0 & 1, uI, uQ, s0 >> 1, P.JB, taps + kDucJA, bI, bQ);
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+        {
+          bI[i] = sat16(bI[i] >> 15);
+          bQ[i] = sat16(bQ[i] >> 15);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+      {
+        bI[i] = (bI[i] * amp + (1 << 14)) >> 15;
+        bQ[i] = (bQ[i] * amp + (1 << 14)) >> 15;
+      }
+      vI[2 * q] = pack16(bI[0], bI[1]);
+      vI[2 * q + 1] = pack16(bI[2], bI[3]);
+      vQ[2 * q] = pack16(bQ[0], bQ[1]);
+      vQ[2 * q + 1] = pack16(bQ[2], bQ[3]);
+    }
+    __syncthreads();
+
+    // 3. stage A, mixer, sum: positions m, m + 1 of pair h (v indices m + LA, m + 1 + LA), outputs (m_t + m) R + i
+    const uint32_t theta_call = ch.theta_ref + (uint32_t)(P.n0 - ch.n_ref) * ch.step;
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+    {
+      const int m = 2 * tid + (kDucTile / 2) * h;
+      if (m >= cnt)
+      {
+        continue;
+      }
+      int aI[2 * R], aQ[2 * R];
+      if (TA == 0)
+      {
+        const uint32_t dI = vI[(m + LA) >> 1], dQ = vQ[(m + LA) >> 1];   // LA = 0: m even, one dword
+#pragma unroll
+        for (int i = 0; i < 2 * R; i++)
+        {
+          aI[i] = (int)(int16_t)(i < R ? dI : dI >> 16);
+          aQ[i] = (int)(int16_t)(i < R ? dQ : dQ >> 16);
+        }
+      }
+      else
+      {
+#pragma unroll
+        for (int i = 0; i < 2 * R; i++)
+        {
+          aI[i] = 1 << 14;
+          aQ[i] = 1 << 14;
+        }
+        const uint32_t *rI = vI + (m >> 1), *rQ = vQ + (m >> 1);
+        for (int t = 0; t < P.JA; t++)
+        {
+          const uint32_t wI = rI[t], wQ = rQ[t];
+#pragma unroll
+          for (int p = 0; p < R; p++)
+          {
+            const uint2 tt = taps[p * P.JA + t];
+            aI[p] = dot2(wI, tt.x, aI[p]);
+            aQ[p] = dot2(wQ, tt.x, aQ[p]);
+            aI[R + p] = dot2(wI, tt.y, aI[R + p]);
+            aQ[R + p] = dot2(wQ, tt.y, aQ[R + p]);
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 2 * R; i++)
+        {
+          aI[i] = sat16(aI[i] >> 15);
+          aQ[i] = sat16(aQ[i] >> 15);
+        }
+      }
+      uint32_t th = theta_call + (uint32_t)((m_t + m) * R) * ch.step;
+#pragma unroll
+      for (int i = 0; i < 2 * R; i++, th += ch.step)
+      {
+        const uint32_t k = ((th + (1u << 19)) >> 20) & 4095u;
+        const uint32_t t = cs[k];                                        // (c, s)
+        const uint32_t cns = (t & 0xffffu) | ((uint32_t)(-(int)(int16_t)(t >> 16)) << 16);   // (c, -s)
+        const uint32_t sc = (t >> 16) | (t << 16);                       // (s, c)
+        const uint32_t a = pack16(aI[i], aQ[i]);
+        sI[h][i] += dot2(a, cns, 1 << 14) >> 15;                         // aI c - aQ s
+        sQ[h][i] += dot2(a, sc, 1 << 14) >> 15;                          // aI s + aQ c
+      }
+    }
+  }
+
+  // output: sat8((S + r) >> s), 2 R samples (4 R bytes) per pair
+  const int sh = (int)P.shift[w];
+  const int r = sh ? 1 << (sh - 1) : 0;
+  uint32_t clipped = 0;
+#pragma unroll
+  for (int h = 0; h < 2; h++)
+  {
+    const int m = 2 * tid + (kDucTile / 2) * h;
+    if (m >= cnt)
+    {
+      continue;
+    }
+    const int n_out = R * min(2, cnt - m);                // outputs of the pair inside the call: 2 R, or R at its end
+    uint32_t word[R];
+#pragma unroll
+    for (int i = 0; i < R; i++)
+    {
+      word[i] = 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < 2 * R; i++)
+    {
+      const int yi = (sI[h][i] + r) >> sh, yq = (sQ[h][i] + r) >> sh;
+      const int oi = min(max(yi, -128), 127), oq = min(max(yq, -128), 127);
+      clipped += (i < n_out) ? (uint32_t)(oi != yi) + (uint32_t)(oq != yq) : 0u;
+      word[i >> 1] |= (((uint32_t)oi & 0xffu) | (((uint32_t)oq & 0xffu) << 8)) << (16 * (i & 1));
+    }
+    int8_t *dst = P.cap + (uint64_t)w * P.cap_stride + 2 * (uint64_t)(m_t + m) * R;
+    const int nb = 2 * n_out;
+    if (nb == 4 * R && ((uintptr_t)dst & 3u) == 0)
+    {
+#pragma unroll
+      for (int i = 0; i < R; i++)
+      {
+        ((uint32_t *)dst)[i] = word[i];
+      }
+    }
+    else
+    {
+      for (int k = 0; k < nb; k++)
+      {
+        dst[k] = (int8_t)(word[k >> 2] >> (8 * (k & 3)));
+      }
+    }
+  }
+  // clip count: a wave reduction, one LDS atomic per wave, one global atomic per workgroup
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+  {
+    clipped += __shfl_xor(clipped, o);
+  }
+  if ((tid & 63) == 0 && clipped != 0u)
+  {
+    atomicAdd(&clip_sum, clipped);
+  }
+  __syncthreads();
+  if (tid == 0 && clip_sum != 0u)
+  {
+    atomicAdd(P.clips + w, (unsigned long long)clip_sum);
+  }
+}
+
+template __global__ void k_duc<1>(const DucParams);
+template __global__ void k_duc<2>(const DucParams);
+template __global__ void k_duc<4>(const DucParams);
+template __global__ void k_duc<8>(const DucParams);
+
+} // namespace hrfd
+
+// ------------------------------------------------------------------ host side
+struct hrfd_duc
+{
+  int device = 0;
+  uint32_t n_captures = 0, n_channels = 0, R = 1;
+  hipStream_t stream = nullptr;
+  hipStream_t last_stream = nullptr;       // the stream of the last launch: the next one is ordered behind it
+  hipEvent_t ev_last = nullptr;            // recorded on last_stream when the next launch runs on another stream
+  hipEvent_t ev_upload = nullptr;          // the last upload from the pinned staging buffer has been read
+  // pinned staging of the records, the channel lists, the shifts and the packed taps (uploads in stream order)
+  hrfd::DucChanDev *h_stage_chan = nullptr;
+  uint32_t *h_stage_u32 = nullptr;         // [W + 1] list offsets, [C] list, [W] shifts
+  uint2 *h_stage_taps = nullptr;
+
+  std::mutex mu;                           // guards the host records (setters may come from another thread)
+  std::vector<hrfd::DucChanDev> h_chan;
+  std::vector<uint32_t> h_shift;
+  std::vector<int16_t> tapsA, tapsB;
+  bool dirty = true;
+  uint64_t N = 0;                          // absolute wideband output-sample counter
+  bool clear_history = true;               // also clears the clip counters
+
+  hrfd::DucChanDev *d_chan = nullptr;
+  uint32_t *d_u32 = nullptr;
+  uint2 *d_taps = nullptr;
+  uint32_t *d_cs = nullptr;
+  unsigned long long *d_clips = nullptr;
+  int8_t *d_hist[2] = {nullptr, nullptr};
+  int cur = 0;
+  int8_t *d_in = nullptr, *d_out = nullptr, *d_tx = nullptr;   // host-path staging and hrfd_duc_transmit's buffer
+  size_t cap_in = 0, cap_out = 0, cap_tx = 0;
+};
+
+static int duc_la(int TA, int R) { return TA > 0 ? (TA - 1) / R : 0; }
+
+static int duc_taps_ok(const char *who, int stage, const int16_t *taps, uint32_t n, uint32_t R)
+{
+  if (stage == 1)
+  {
+    return ddc_taps_ok(who, taps, n, hrfd::kDucMaxTB);
+  }
+  if (n > (uint32_t)hrfd::kDucMaxTA || (n > 0 && taps == nullptr))
+  {
+    return fail(HRFD_EINVAL, "%s: %u taps (at most %d, and a tap array when n > 0)", who, n, hrfd::kDucMaxTA);
+  }
+  for (uint32_t p = 0; p < R; p++)
+  {
+    int64_t sum = 0;
+    for (uint32_t k = p; k < n; k += R)
+    {
+      sum += taps[k] < 0 ? -(int64_t)taps[k] : (int64_t)taps[k];
+    }
+    if (sum > 65535)
+    {
+      return fail(HRFD_EINVAL, "%s: branch %u has sum |h| = %lld > 65535 (the int32 accumulator could overflow)", who, p,
+                  (long long)sum);
+    }
+  }
+  return HRFD_OK;
+}
+
+static void duc_free(hrfd_duc *d)
+{
+  (void)hipSetDevice(d->device);
+  if (d->stream)
+  {
+    (void)hipStreamSynchronize(d->stream);
+  }
+  if (d->last_stream && d->last_stream != d->stream)
+  {
+    (void)hipStreamSynchronize(d->last_stream);
+  }
+  void *ptrs[] = {d->d_chan, d->d_u32, d->d_taps, d->d_cs, d->d_clips, d->d_hist[0], d->d_hist[1], d->d_in, d->d_out, d->d_tx};
+  for (void *p : ptrs)
+  {
+    if (p) (void)hipFree(p);
+  }
+  if (d->h_stage_chan) (void)hipHostFree(d->h_stage_chan);
+  if (d->h_stage_u32) (void)hipHostFree(d->h_stage_u32);
+  if (d->h_stage_taps) (void)hipHostFree(d->h_stage_taps);
+  if (d->ev_last) (void)hipEventDestroy(d->ev_last);
+  if (d->ev_upload) (void)hipEventDestroy(d->ev_upload);
+  if (d->stream) (void)hipStreamDestroy(d->stream);
+  delete d;
+}
+
+extern "C" int hrfd_duc_create(uint32_t n_captures, uint32_t n_channels, uint32_t interpolation, int device, hrfd_duc **out)
+{
+  if (out != nullptr)
+  {
+    *out = nullptr;
+  }
+  if (out == nullptr || n_captures == 0 || n_channels == 0)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_create: need n_captures > 0, n_channels > 0 and a result pointer");
+  }
+  if (n_channels > hrfd::kDucMaxChannels)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_create: at most %u channels (the int32 sums), got %u", hrfd::kDucMaxChannels,
+                n_channels);
+  }
+  if (interpolation != 1 && interpolation != 2 && interpolation != 4 && interpolation != 8)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_create: interpolation must be 1, 2, 4 or 8 (got %u)", interpolation);
+  }
+  if (n_captures > 65536)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_create: at most 65536 captures (got %u)", n_captures);
+  }
+  if (hrfd_device_count() <= 0)
+  {
+    return fail(HRFD_ENODEV, "hrfd_duc_create: no HIP device visible (this library has no CPU path)");
+  }
+  if (device < 0)
+  {
+    HIP_TRY(hipGetDevice(&device));
+  }
+  HIP_TRY(hipSetDevice(device));
+  hrfd_duc *d = new hrfd_duc;
+  d->device = device;
+  d->n_captures = n_captures;
+  d->n_channels = n_channels;
+  d->R = interpolation;
+  d->h_chan.assign(n_channels, hrfd::DucChanDev{0u, 0u, 0u, 32768u, 0ull});
+  d->h_shift.assign(n_captures, 8u);
+  switch (interpolation)
+  {
+  case 2: d->tapsA.assign(hrfd::Q_DUC_A2, hrfd::Q_DUC_A2 + hrfd::N_DUC_A2); break;
+  case 4: d->tapsA.assign(hrfd::Q_DUC_A4, hrfd::Q_DUC_A4 + hrfd::N_DUC_A4); break;
+  case 8: d->tapsA.assign(hrfd::Q_DUC_A8, hrfd::Q_DUC_A8 + hrfd::N_DUC_A8); break;
+  default: break;                          // R = 1: stage A holds
+  }
+  d->tapsB.assign(hrfd::Q_DDC_B, hrfd::Q_DDC_B + hrfd::N_DDC_B);
+  std::vector<uint32_t> cs(4096);
+  for (int k = 0; k < 4096; k++)
+  {
+    cs[k] = (uint16_t)hrfd::Q_DDC_COS[k] | ((uint32_t)(uint16_t)hrfd::Q_DDC_COS[(k - 1024) & 4095] << 16);
+  }
+  const size_t hist_bytes = (size_t)n_channels * hrfd::kDucH * 2;
+  const size_t n_u32 = 2 * (size_t)n_captures + 1 + n_channels;
+  const size_t n_taps = hrfd::kDucJA + hrfd::kDucJB;
+  bool ok = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) == hipSuccess;
+  ok = ok && hipMalloc((void **)&d->d_chan, sizeof(hrfd::DucChanDev) * n_channels) == hipSuccess;
+  ok = ok && hipMalloc((void **)&d->d_u32, sizeof(uint32_t) * n_u32) == hipSuccess;
+  ok = ok && hipMalloc((void **)&d->d_taps, sizeof(uint2) * n_taps) == hipSuccess;
+  ok = ok && hipMalloc((void **)&d->d_cs, sizeof(uint32_t) * 4096) == hipSuccess;
+  ok = ok && hipMalloc((void **)&d->d_clips, sizeof(unsigned long long) * n_captures) == hipSuccess;
+  ok = ok && hipMalloc((void **)&d->d_hist[0], hist_bytes) == hipSuccess;
+  ok = ok && hipMalloc((void **)&d->d_hist[1], hist_bytes) == hipSuccess;
+  ok = ok && hipMemcpy(d->d_cs, cs.data(), sizeof(uint32_t) * 4096, hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&d->ev_last, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&d->ev_upload, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipHostMalloc((void **)&d->h_stage_chan, sizeof(hrfd::DucChanDev) * n_channels, hipHostMallocDefault) == hipSuccess;
+  ok = ok && hipHostMalloc((void **)&d->h_stage_u32, sizeof(uint32_t) * n_u32, hipHostMallocDefault) == hipSuccess;
+  ok = ok && hipHostMalloc((void **)&d->h_stage_taps, sizeof(uint2) * n_taps, hipHostMallocDefault) == hipSuccess;
+  if (!ok)
+  {
+    (void)hipGetLastError();
+    duc_free(d);
+    return fail(HRFD_ENOMEM, "hrfd_duc_create: device allocation failed");
+  }
+  d->last_stream = d->stream;
+  *out = d;
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_destroy(hrfd_duc *d)
+{
+  if (d != nullptr)
+  {
+    duc_free(d);
+  }
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_reset(hrfd_duc *d)
+{
+  if (d == nullptr)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_reset: NULL handle");
+  }
+  std::lock_guard<std::mutex> g(d->mu);
+  d->N = 0;
+  for (hrfd::DucChanDev &c : d->h_chan)
+  {
+    c.theta_ref = 0u;
+    c.n_ref = 0ull;
+  }
+  d->clear_history = true;
+  d->dirty = true;
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_set_tuning(hrfd_duc *d, uint32_t channel, uint32_t capture, uint32_t step)
+{
+  if (d == nullptr || channel >= d->n_channels || capture >= d->n_captures)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_set_tuning: bad handle, channel or capture");
+  }
+  std::lock_guard<std::mutex> g(d->mu);
+  hrfd::DucChanDev &c = d->h_chan[channel];
+  // phase-continuous at the change point: theta_ref = theta(N) under the old tuning
+  c.theta_ref = c.theta_ref + (uint32_t)(d->N - c.n_ref) * c.step;
+  c.n_ref = d->N;
+  c.step = step;
+  c.capture = capture;
+  d->dirty = true;
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_set_amplitude(hrfd_duc *d, uint32_t channel, uint32_t amplitude)
+{
+  if (amplitude > 32768u)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_set_amplitude: A must be 0..32768 (got %u)", amplitude);
+  }
+  if (d == nullptr || (channel >= d->n_channels && channel != HRFD_ALL_CHANNELS))
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_set_amplitude: bad handle or channel");
+  }
+  std::lock_guard<std::mutex> g(d->mu);
+  for (uint32_t c = 0; c < d->n_channels; c++)
+  {
+    if (channel == HRFD_ALL_CHANNELS || c == channel)
+    {
+      d->h_chan[c].amp = amplitude;
+    }
+  }
+  d->dirty = true;
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_set_output_shift(hrfd_duc *d, uint32_t capture, uint32_t s)
+{
+  if (s > hrfd::kDucMaxShift)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_set_output_shift: s must be 0..%u (got %u)", hrfd::kDucMaxShift, s);
+  }
+  if (d == nullptr || (capture >= d->n_captures && capture != HRFD_ALL_CHANNELS))
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_set_output_shift: bad handle or capture");
+  }
+  std::lock_guard<std::mutex> g(d->mu);
+  for (uint32_t w = 0; w < d->n_captures; w++)
+  {
+    if (capture == HRFD_ALL_CHANNELS || w == capture)
+    {
+      d->h_shift[w] = s;
+    }
+  }
+  d->dirty = true;
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_set_filter(hrfd_duc *d, int stage, const int16_t *taps, uint32_t n)
+{
+  if (stage != 0 && stage != 1)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_set_filter: stage must be 0 (A) or 1 (B) (got %d)", stage);
+  }
+  // the tap count, and stage B's sum, need no handle; stage A's bound is per polyphase branch of the handle's R
+  int rc = duc_taps_ok("hrfd_duc_set_filter", stage, taps, n, 1u);
+  if (rc != HRFD_OK && (stage == 1 || n > (uint32_t)hrfd::kDucMaxTA || (n > 0 && taps == nullptr)))
+  {
+    return rc;
+  }
+  if (d == nullptr)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_set_filter: NULL handle");
+  }
+  if ((rc = duc_taps_ok("hrfd_duc_set_filter", stage, taps, n, d->R)) != HRFD_OK)
+  {
+    return rc;
+  }
+  std::lock_guard<std::mutex> g(d->mu);
+  (stage == 0 ? d->tapsA : d->tapsB).assign(taps, taps + n);
+  d->dirty = true;
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_get_phase(hrfd_duc *d, uint32_t channel, uint32_t *theta)
+{
+  if (d == nullptr || channel >= d->n_channels || theta == nullptr)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_get_phase: bad handle, channel or NULL result");
+  }
+  std::lock_guard<std::mutex> g(d->mu);
+  const hrfd::DucChanDev &c = d->h_chan[channel];
+  *theta = c.theta_ref + (uint32_t)(d->N - c.n_ref) * c.step;
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_get_clips(hrfd_duc *d, uint32_t capture, uint64_t *n)
+{
+  if (d == nullptr || capture >= d->n_captures || n == nullptr)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_get_clips: bad handle, capture or NULL result");
+  }
+  HIP_TRY(hipSetDevice(d->device));
+  {
+    std::lock_guard<std::mutex> g(d->mu);
+    if (d->clear_history)
+    {
+      *n = 0;                              // no launch since create or reset
+      return HRFD_OK;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(d->last_stream));
+  unsigned long long v = 0;
+  HIP_TRY(hipMemcpy(&v, d->d_clips + capture, sizeof(v), hipMemcpyDeviceToHost));
+  *n = (uint64_t)v;
+  return HRFD_OK;
+}
+
+// stage A's taps as R branches of LA + 1 taps each, packed like ddc_pack_taps: branch p, tap j = hA[p + j R]
+static void duc_pack_taps_a(const std::vector<int16_t> &h, int R, uint2 *out, int JA)
+{
+  const int T = (int)h.size();
+  const int LA = duc_la(T, R);
+  for (int p = 0; p < R; p++)
+  {
+    std::vector<int16_t> hp(LA + 1, 0);
+    for (int j = 0; j <= LA; j++)
+    {
+      hp[j] = (p + j * R < T) ? h[p + j * R] : (int16_t)0;
+    }
+    ddc_pack_taps(hp, out + p * JA, JA);
+  }
+}
+
+// one launch over every capture on `s`: R * in_bytes per capture from in_bytes per channel
+static int duc_launch(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_stride, uint32_t in_bytes, int8_t *d_captures,
+                      uint64_t capture_stride, hipStream_t s)
+{
+  using namespace hrfd;
+  // The history ping-pong, the records and the clip counters are the handle's: a launch on another stream than the last
+  // one waits for it on the device.
+  if (s != d->last_stream)
+  {
+    HIP_TRY(hipEventRecord(d->ev_last, d->last_stream));
+    HIP_TRY(hipStreamWaitEvent(s, d->ev_last, 0));
+  }
+  const uint32_t W = d->n_captures, C = d->n_channels;
+  DucParams P;
+  {
+    std::lock_guard<std::mutex> g(d->mu);
+    P.TA = (int)d->tapsA.size();
+    P.TB = (int)d->tapsB.size();
+    P.LA = duc_la(P.TA, (int)d->R);
+    P.JA = P.TA > 0 ? ddc_packed_len(P.LA + 1) : 0;
+    P.JB = ddc_packed_len(P.TB);
+    if (d->dirty || d->clear_history)
+    {
+      // records, channel lists, shifts, taps and a cleared history go to the device on `s`, ahead of this launch; the
+      // pinned staging buffers are rewritten only once the device has read the previous upload out of them
+      HIP_TRY(hipEventSynchronize(d->ev_upload));
+      memcpy(d->h_stage_chan, d->h_chan.data(), sizeof(DucChanDev) * C);
+      uint32_t *off = d->h_stage_u32, *list = off + W + 1, *shift = list + C;
+      std::vector<uint32_t> count(W, 0u);
+      for (uint32_t c = 0; c < C; c++)
+      {
+        count[d->h_chan[c].capture]++;
+      }
+      off[0] = 0;
+      for (uint32_t w = 0; w < W; w++)
+      {
+        off[w + 1] = off[w] + count[w];
+        count[w] = off[w];
+      }
+      for (uint32_t c = 0; c < C; c++)
+      {
+        list[count[d->h_chan[c].capture]++] = c;
+      }
+      memcpy(shift, d->h_shift.data(), sizeof(uint32_t) * W);
+      memset(d->h_stage_taps, 0, sizeof(uint2) * (kDucJA + kDucJB));
+      if (P.TA > 0)
+      {
+        duc_pack_taps_a(d->tapsA, (int)d->R, d->h_stage_taps, P.JA);
+      }
+      ddc_pack_taps(d->tapsB, d->h_stage_taps + kDucJA, P.JB);
+      HIP_TRY(hipMemcpyAsync(d->d_chan, d->h_stage_chan, sizeof(DucChanDev) * C, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(d->d_u32, d->h_stage_u32, sizeof(uint32_t) * (2 * (size_t)W + 1 + C), hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(d->d_taps, d->h_stage_taps, sizeof(uint2) * (kDucJA + kDucJB), hipMemcpyHostToDevice, s));
+      HIP_TRY(hipEventRecord(d->ev_upload, s));
+      if (d->clear_history)
+      {
+        HIP_TRY(hipMemsetAsync(d->d_hist[d->cur], 0, (size_t)C * kDucH * 2, s));
+        HIP_TRY(hipMemsetAsync(d->d_clips, 0, sizeof(unsigned long long) * W, s));
+        d->clear_history = false;
+      }
+      d->dirty = false;
+    }
+    P.n0 = d->N;
+    d->N += (uint64_t)d->R * (in_bytes / 2u);   // under the same lock as the read: a setter sees N before or after
+  }
+  P.in = d_channels;
+  P.in_stride = channel_stride;
+  P.hist_in = d->d_hist[d->cur];
+  P.hist_out = d->d_hist[d->cur ^ 1];
+  P.cap = d_captures;
+  P.cap_stride = capture_stride;
+  P.chan = d->d_chan;
+  P.list_off = d->d_u32;
+  P.list = d->d_u32 + W + 1;
+  P.shift = d->d_u32 + W + 1 + C;
+  P.taps = d->d_taps;
+  P.cs = d->d_cs;
+  P.clips = d->d_clips;
+  P.M = in_bytes / 2u;
+  P.n_tiles = (P.M + kDucTile - 1) / kDucTile;
+  P.n_channels = C;
+  P.n_captures = W;
+  const dim3 grid(P.n_tiles * W + C);
+  switch (d->R)
+  {
+  case 1: hipLaunchKernelGGL(k_duc<1>, grid, dim3(kDucThreads), 0, s, P); break;
+  case 2: hipLaunchKernelGGL(k_duc<2>, grid, dim3(kDucThreads), 0, s, P); break;
+  case 4: hipLaunchKernelGGL(k_duc<4>, grid, dim3(kDucThreads), 0, s, P); break;
+  default: hipLaunchKernelGGL(k_duc<8>, grid, dim3(kDucThreads), 0, s, P); break;
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+  {
+    // the counter and the history advance only with a launch that was accepted
+    std::lock_guard<std::mutex> g(d->mu);
+    d->N = P.n0;
+    return fail(HRFD_ENODEV, "k_duc launch failed: %s", hipGetErrorString(e));
+  }
+  d->cur ^= 1;
+  d->last_stream = s;
+  return HRFD_OK;
+}
+
+static int duc_check_call(hrfd_duc *d, const void *channels, uint64_t channel_stride, uint32_t in_bytes, const void *captures,
+                          uint64_t capture_stride, const char *who)
+{
+  if (d == nullptr || channels == nullptr || captures == nullptr)
+  {
+    return fail(HRFD_EINVAL, "%s: NULL argument", who);
+  }
+  if (in_bytes < 2 || (in_bytes & 1u) != 0 || in_bytes > (1u << 25))
+  {
+    return fail(HRFD_EINVAL, "%s: in_bytes must be even, >= 2 and <= 2^25 (got %u)", who, in_bytes);
+  }
+  // one launch: gridDim.x * blockDim.x work-items must fit in 32 bits
+  if ((uint64_t)d->n_captures * ((in_bytes / 2u + hrfd::kDucTile - 1) / hrfd::kDucTile) + d->n_channels >
+      0xffffffffull / hrfd::kDucThreads)
+  {
+    return fail(HRFD_EINVAL, "%s: %u captures x %u bytes need more workgroups than one launch takes", who, d->n_captures,
+                in_bytes);
+  }
+  if (channel_stride < in_bytes || capture_stride < (uint64_t)d->R * in_bytes || (channel_stride & 1u) != 0 ||
+      ((uintptr_t)channels & 1u) != 0)
+  {
+    return fail(HRFD_EINVAL, "%s: strides shorter than a row, or an odd channel stride / address", who);
+  }
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_process_device(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_stride, uint32_t in_bytes,
+                                       int8_t *d_captures, uint64_t capture_stride, void *stream)
+{
+  int rc = duc_check_call(d, d_channels, channel_stride, in_bytes, d_captures, capture_stride, "hrfd_duc_process_device");
+  if (rc != HRFD_OK)
+  {
+    return rc;
+  }
+  HIP_TRY(hipSetDevice(d->device));
+  return duc_launch(d, d_channels, channel_stride, in_bytes, d_captures, capture_stride,
+                    stream ? (hipStream_t)stream : d->stream);
+}
+
+extern "C" int hrfd_duc_process(hrfd_duc *d, const int8_t *channels, uint32_t in_bytes, int8_t *captures)
+{
+  int rc = duc_check_call(d, channels, in_bytes, in_bytes, captures, d ? (uint64_t)d->R * in_bytes : 0, "hrfd_duc_process");
+  if (rc != HRFD_OK)
+  {
+    return rc;
+  }
+  HIP_TRY(hipSetDevice(d->device));
+  hipStream_t s = d->stream;
+  HIP_TRY(hipStreamSynchronize(s));
+  if (d->last_stream != s)
+  {
+    HIP_TRY(hipStreamSynchronize(d->last_stream));     // the staging buffers may still be read by the last launch
+  }
+  const size_t in_total = (size_t)d->n_channels * in_bytes, out_total = (size_t)d->n_captures * d->R * in_bytes;
+  if ((rc = grow((void **)&d->d_in, &d->cap_in, in_total)) != HRFD_OK) return rc;
+  if ((rc = grow((void **)&d->d_out, &d->cap_out, out_total)) != HRFD_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(d->d_in, channels, in_total, hipMemcpyHostToDevice, s));
+  if ((rc = duc_launch(d, d->d_in, in_bytes, in_bytes, d->d_out, (uint64_t)d->R * in_bytes, s)) != HRFD_OK)
+  {
+    return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(captures, d->d_out, out_total, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pcm, uint32_t n_per_channel,
+                                 int8_t *d_captures, uint64_t capture_stride, void *stream)
+{
+  if (mod == nullptr || d_pcm == nullptr || n_per_channel == 0 || n_per_channel > (1u << 16))
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_transmit: NULL argument, or n_per_channel not in 1..65536 (got %u)", n_per_channel);
+  }
+  if (d != nullptr && mod->n_channels != d->n_channels)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_transmit: the modulator has %u channels, the DUC %u", mod->n_channels, d->n_channels);
+  }
+  const uint32_t in_bytes = 512u * n_per_channel;
+  int rc = duc_check_call(d, d_pcm, in_bytes, in_bytes, d_captures, capture_stride, "hrfd_duc_transmit");
+  if (rc != HRFD_OK)
+  {
+    return rc;
+  }
+  if (mod->device != d->device)
+  {
+    return fail(HRFD_EINVAL, "hrfd_duc_transmit: the modulator lives on device %d, the DUC on %d", mod->device, d->device);
+  }
+  HIP_TRY(hipSetDevice(d->device));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  const size_t need = (size_t)d->n_channels * in_bytes;
+  if (need > d->cap_tx)
+  {
+    HIP_TRY(hipStreamSynchronize(d->last_stream));      // the last launch may still read the old buffer
+    if ((rc = grow((void **)&d->d_tx, &d->cap_tx, need)) != HRFD_OK) return rc;
+  }
+  // the modulator overwrites the buffer the handle's last launch reads: behind it on the device
+  if (s != d->last_stream)
+  {
+    HIP_TRY(hipEventRecord(d->ev_last, d->last_stream));
+    HIP_TRY(hipStreamWaitEvent(s, d->ev_last, 0));
+  }
+  if ((rc = hrfd_mod_process_device(mod, d_pcm, n_per_channel, d->d_tx, s)) != HRFD_OK)
+  {
+    return rc;
+  }
+  return duc_launch(d, d->d_tx, in_bytes, in_bytes, d_captures, capture_stride, s);
+}

@@ -16,3 +16,4 @@
 #include "hrfd_play.hip"
 #include "hrfd_membw.hip"
 #include "hrfd_ddc.hip"
+#include "hrfd_duc.hip"

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "hrfd_ddc_tables.h"
+#include "hrfd_duc_tables.h"
 
 namespace hrfd {
 
@@ -161,6 +162,9 @@ static const NamedTable kNamedTables[] = {
   {"DDC_A4", Q_DDC_A4, N_DDC_A4},
   {"DDC_A8", Q_DDC_A8, N_DDC_A8},
   {"DDC_B", Q_DDC_B, N_DDC_B},
+  {"DUC_A2", Q_DUC_A2, N_DUC_A2},
+  {"DUC_A4", Q_DUC_A4, N_DUC_A4},
+  {"DUC_A8", Q_DUC_A8, N_DUC_A8},
 };
 
 } // namespace hrfd

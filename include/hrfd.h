@@ -404,10 +404,63 @@ int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captures, uint64_
                      uint32_t *d_magnitude, uint8_t *d_signal_allowed, uint32_t *n_replayed);
 
 /* ------------------------------------------------------------------------------
+ * DUC bank: C channel streams at 2.048 MS/s -> W wideband captures (the DDC's mirror; the reference transmits one station
+ * per HackRF, at DC of the stream, Radio.cc:1697-1722).  A channel stream is int8 IQ at 2.048 MS/s, what hrfd_mod_*
+ * writes; a call consumes in_bytes bytes (even, >= 2) of every channel and produces R * in_bytes bytes of int8 IQ per
+ * capture at R x 2.048 MS/s, R = 1, 2, 4, 8.  Exact integer arithmetic, the same on every device (tests/duc_model.py
+ * restates it); m counts channel samples, n = m R + p wideband samples:
+ *   N        absolute wideband output-sample counter of the handle (uint64), advanced by R * in_bytes / 2 per call; every
+ *            channel keeps its last H = 318 samples (zeros after create and reset: silence before the first call)
+ *   tuning   channel -> (capture, step, theta_ref, N_ref); sample n is mixed with theta(n) = theta_ref + (n - N_ref) step
+ *            mod 2^32, set_tuning at counter N is phase-continuous, exactly as the DDC's.  step = round(f / (R 2 048 000)
+ *            2^32) mod 2^32 puts the channel's DC at +f (no 64 kHz shift: the reference transmits the station at DC)
+ *   input    u[m] = x[m] << 8 (x the int8 I or Q)
+ *   stage B  b[m] = sat16((sum_k hB[k] u[m - k] + 2^14) >> 15), T_B <= 256 taps, sum |hB| <= 65535; T_B = 0: b = u
+ *   amplitude v[m] = (b[m] A + 2^14) >> 15, A = 0..32768 per channel (default 32768: v = b; A = 0 mutes the channel)
+ *   stage A  a[n] = sat16((sum_{k : (n - k) mod R = 0} hA[k] v[(n - k) / R] + 2^14) >> 15), the zero-stuffed
+ *            interpolation, T_A <= 64 taps, sum |hA[k]| over k = p mod R <= 65535 for every branch p; T_A = 0: a[n] = v[n / R]
+ *   mixer    k = ((theta + 2^19) >> 20) & 4095, c = COS[k], s = COS[(k - 1024) & 4095] (the DDC's table), multiplication
+ *            by e^{+j theta}: yI = (aI c - aQ s + 2^14) >> 15, yQ = (aQ c + aI s + 2^14) >> 15 (int32, |y| <= 46 341)
+ *   sum      S_w[n] = sum of y over the channels mapped to capture w (int32: n_channels <= 32768 cannot overflow it)
+ *   output   sat8((S + r) >> s), r = s ? 1 << (s - 1) : 0; s = 0..24 per capture (default 8: one full-scale channel comes
+ *            out at full scale).  Every output sample (I and Q counted apart) whose sat8 clipped adds 1 to the capture's
+ *            uint64 clip counter (0 after create and reset).
+ * Default filters (hrfd_duc_tables.h, tools/duc_design.py; hrfd_q15_table "DUC_A2", "DUC_A4", "DUC_A8"): stage A
+ * +-220 kHz passband, >= 60 dB from 2.048 MHz - 220 kHz, DC gain R (hold at R = 1); stage B the DDC's "DDC_B" (+-164 kHz,
+ * >= 60 dB beyond +-220 kHz).  A call applies the filters current at its start to the channel streams, history included.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well); setters never wait for the
+ * device: the records and taps a setter changed are copied to the device on the next call's stream, ahead of its launch.
+ * Calls may use different streams: each launch is ordered on the device behind the handle's previous one.
+ *   hrfd_duc_process          host buffers: channels [C][in_bytes] -> captures [W][R * in_bytes]; blocking
+ *   hrfd_duc_process_device   device buffers, rows channel_stride / capture_stride bytes apart; asynchronous on `stream`
+ *                             (a hipStream_t, NULL = the handle's own)
+ *   hrfd_duc_transmit         the modulator bank (mod->n_channels == C, the same device) into a buffer of the handle,
+ *                             [C][512 * n_per_channel], then the DUC over it, both on `stream`: outputs exactly those of
+ *                             hrfd_mod_process_device followed by hrfd_duc_process_device; asynchronous
+ *   hrfd_duc_get_clips        waits for the handle's last launch, then reads the capture's clip counter
+ */
+typedef struct hrfd_duc hrfd_duc;
+int hrfd_duc_create(uint32_t n_captures, uint32_t n_channels, uint32_t interpolation, int device, hrfd_duc **out);
+int hrfd_duc_destroy(hrfd_duc *d);
+int hrfd_duc_reset(hrfd_duc *d);              /* history 0, N = 0, every theta_ref = N_ref = 0, clip counters 0 */
+int hrfd_duc_set_tuning(hrfd_duc *d, uint32_t channel, uint32_t capture, uint32_t step);
+int hrfd_duc_set_amplitude(hrfd_duc *d, uint32_t channel, uint32_t amplitude);    /* HRFD_ALL_CHANNELS allowed */
+int hrfd_duc_set_output_shift(hrfd_duc *d, uint32_t capture, uint32_t s);         /* HRFD_ALL_CHANNELS: every capture */
+int hrfd_duc_set_filter(hrfd_duc *d, int stage, const int16_t *taps, uint32_t n); /* stage 0 = A, 1 = B; n = 0: bypass */
+int hrfd_duc_get_phase(hrfd_duc *d, uint32_t channel, uint32_t *theta);          /* theta(N) */
+int hrfd_duc_get_clips(hrfd_duc *d, uint32_t capture, uint64_t *n);
+int hrfd_duc_process(hrfd_duc *d, const int8_t *channels, uint32_t in_bytes, int8_t *captures);
+int hrfd_duc_process_device(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_stride, uint32_t in_bytes,
+                            int8_t *d_captures, uint64_t capture_stride, void *stream);
+int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pcm, uint32_t n_per_channel, int8_t *d_captures,
+                      uint64_t capture_stride, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",
- * "INTERP_HB1","INTERPSIG_S1", and the DDC bank's "DDC_COS" (4096 entries), "DDC_A2","DDC_A4","DDC_A8","DDC_B" (Q15 taps).
+ * "INTERP_HB1","INTERPSIG_S1", and the DDC bank's "DDC_COS" (4096 entries), "DDC_A2","DDC_A4","DDC_A8","DDC_B" (Q15 taps),
+ * and the DUC bank's "DUC_A2","DUC_A4","DUC_A8" (Q15 taps).
  * Copies min(cap, count) entries (out may be NULL to ask for the count) and returns the count, 0 if unknown. */
 int hrfd_q15_table(const char *name, int16_t *out, int cap);
 /* host-built atan2 table [256][256] (float bits) and dBFS table [257] */
