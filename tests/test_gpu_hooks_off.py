@@ -39,6 +39,7 @@ GROUPS = [
     ("receive_everything_else", "test_gpu_rx", "", 120),
     ("ddc_bank", "test_gpu_ddc", "", 36),
     ("ddc_edges", "test_gpu_ddc_edges", "", 36),
+    ("squelch_sweep", "test_gpu_squelch_sweep", "", 40),
 ]
 
 
