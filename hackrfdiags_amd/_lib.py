@@ -190,6 +190,16 @@ def load() -> C.CDLL:
         L.hrfd_duc_process.argtypes = [_vp, _vp, C.c_uint32, _vp]
         L.hrfd_duc_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp]
         L.hrfd_duc_transmit.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp]
+    if hasattr(L, "hrfd_spec_create"):                     # (an older build named by HRFD_LIB has no spectrum bank)
+        _u64p = C.POINTER(C.c_uint64)
+        L.hrfd_spec_create.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_spec_destroy.argtypes = [_vp]
+        L.hrfd_spec_set_window.argtypes = [_vp, _i16p]
+        L.hrfd_spec_set_band.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]
+        L.hrfd_spec_clear_bands.argtypes = [_vp]
+        L.hrfd_spec_n_bands.argtypes = [_vp, _u32p]
+        L.hrfd_spec_process.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp, _vp]
+        L.hrfd_spec_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

@@ -665,6 +665,143 @@ class Duc:
         check(self.L.hrfd_duc_transmit(self.h, mod.h, _ptr(d_pcm), int(n_per_channel), _ptr(d_captures),
                                        int(capture_stride), _ptr(stream)), "hrfd_duc_transmit")
 
+SPEC_MAX_FRAMES = 65536
+SPEC_MAX_THRESHOLD = 1 << 44
+# Full scale of the spectrum bank, from the model (tests/spec_model.py): a tone of amplitude 127 on a bin centre under the
+# default window.  The window scales it by w / 256 (mean of the Hann table: 32767 / 2), the transform divides by N, so the
+# bin holds |X| = 127 * (32767 / 2) / 256 = 8127.8 and p = |X|^2 per frame, whatever N is.  0 dBFS is that power in one bin.
+SPEC_FULL_SCALE_POWER = (127.0 * 32767.0 / 512.0) ** 2
+
+
+def spec_bin_hz(decimation: int, log2_n: int) -> float:
+    """width of one bin: R * 2 048 000 / N Hz"""
+    return int(decimation) * DDC_FS_OUT / float(1 << int(log2_n))
+
+
+def spec_offsets_hz(decimation: int, log2_n: int) -> np.ndarray:
+    """offset from the capture's centre of every natural-order bin (k >= N / 2 are the negative offsets)"""
+    n = 1 << int(log2_n)
+    k = np.arange(n)
+    return np.where(k < n // 2, k, k - n) * spec_bin_hz(decimation, log2_n)
+
+
+def spec_dbfs(power, n_frames: int, floor_db: float = -200.0) -> np.ndarray:
+    """for display: 10 log10(power per frame / SPEC_FULL_SCALE_POWER), empty bins at floor_db"""
+    p = np.asarray(power, dtype=np.float64) / (float(n_frames) * SPEC_FULL_SCALE_POWER)
+    return np.where(p > 0, 10 * np.log10(np.maximum(p, 1e-300)), floor_db).clip(min=floor_db)
+
+
+def spec_threshold(dbfs: float, n_bins: int = 1) -> int:
+    """spec_dbfs's inverse for set_band: the power per frame of n_bins bins that each stand at dbfs"""
+    t = int(round(SPEC_FULL_SCALE_POWER * 10.0 ** (float(dbfs) / 10.0) * int(n_bins)))
+    return min(max(t, 0), SPEC_MAX_THRESHOLD)
+
+
+def find_stations(power, n_frames: int, decimation: int, log2_n: int, bandwidth_hz: float, raster_hz: float,
+                  min_db_over_floor: float, floor_percentile: float = 25.0):
+    """[(capture, offset_hz, band_power)] of the stations in power [W, N] (Spectrum.process): the sums of every window of
+    bandwidth_hz (exact integers, circular over the bins), the floor of a capture = the floor_percentile of those sums,
+    candidates = windows at least min_db_over_floor above it that are the largest within one bandwidth on either side
+    (the earlier bin wins a tie), centres snapped to the raster.  Sorted by capture, then offset."""
+    P = np.asarray(power, dtype=np.uint64)
+    n = 1 << int(log2_n)
+    P = P.reshape(-1, n)
+    bin_hz = spec_bin_hz(decimation, log2_n)
+    nb = min(n, max(1, int(round(float(bandwidth_hz) / bin_hz))))
+    ratio = 10.0 ** (float(min_db_over_floor) / 10.0)
+    found = []
+    for w in range(P.shape[0]):
+        row = [int(v) for v in P[w]]
+        cum = [0]
+        for v in row + row[:nb]:
+            cum.append(cum[-1] + v)
+        sums = [cum[i + nb] - cum[i] for i in range(n)]             # window starting at bin i
+        floor = float(np.percentile(np.asarray(sums, dtype=np.float64), floor_percentile))
+        order = sorted(range(n), key=lambda i: (-sums[i], i))
+        taken = []
+        for i in order:
+            if not float(sums[i]) >= ratio * max(floor, 1.0):        # the one float comparison
+                break
+            if all(min((i - j) % n, (j - i) % n) >= nb for j in taken):
+                taken.append(i)
+        for i in taken:
+            centre = (i + (nb - 1) / 2.0) % n
+            off = (centre if centre < n / 2 else centre - n) * bin_hz
+            found.append((w, float(round(off / float(raster_hz)) * float(raster_hz)), sums[i]))
+    found.sort(key=lambda t: (t[0], t[1]))
+    return found
+
+
+def tune_from_scan(ddc: "Ddc", stations, first_channel: int = 0):
+    """Ddc.tune(channel, capture, offset_hz) for every station of find_stations, channels counted from first_channel
+    (tune adds the 64 kHz of Radio.cc:1191); returns {channel: (capture, offset_hz)}"""
+    chan_map = {}
+    for i, (capture, offset_hz, _) in enumerate(stations):
+        ddc.tune(first_channel + i, capture, offset_hz)
+        chan_map[first_channel + i] = (capture, offset_hz)
+    return chan_map
+
+
+class Spectrum:
+    """A bank of windowed integer FFTs (hrfd_spec_*): n_captures wideband int8 IQ captures at decimation x 2.048 MS/s in,
+    the power of every bin of a 2^log2_n point transform summed over a call's frames out, and the verdicts of the bands."""
+
+    def __init__(self, n_captures: int, decimation: int, log2_n: int, device: int = -1):
+        self.L = _lib.load()
+        self.W, self.R, self.log2_n, self.N = int(n_captures), int(decimation), int(log2_n), 1 << int(log2_n)
+        h = C.c_void_p()
+        check(self.L.hrfd_spec_create(self.W, self.R, self.log2_n, device, C.byref(h)), "hrfd_spec_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hrfd_spec_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_window(self, w=None):
+        """N int16 values; None restores the default (Hann)"""
+        if w is None:
+            check(self.L.hrfd_spec_set_window(self.h, None), "hrfd_spec_set_window")
+            return
+        t = np.ascontiguousarray(w, dtype=np.int16)
+        if t.size != self.N:
+            raise ValueError(f"the window needs {self.N} entries, got {t.size}")
+        check(self.L.hrfd_spec_set_window(self.h, t.ctypes.data_as(C.POINTER(C.c_int16))), "hrfd_spec_set_window")
+
+    def set_band(self, band: int, capture: int, first_bin: int, n_bins: int, threshold: int):
+        """band == n_bands appends; bins modulo N; threshold in power units per frame (spec_threshold)"""
+        check(self.L.hrfd_spec_set_band(self.h, int(band), int(capture), int(first_bin), int(n_bins), int(threshold)),
+              "hrfd_spec_set_band")
+
+    def clear_bands(self):
+        check(self.L.hrfd_spec_clear_bands(self.h), "hrfd_spec_clear_bands")
+
+    @property
+    def n_bands(self) -> int:
+        v = C.c_uint32(0)
+        check(self.L.hrfd_spec_n_bands(self.h, C.byref(v)), "hrfd_spec_n_bands")
+        return int(v.value)
+
+    def process(self, captures: np.ndarray, n_frames: int):
+        """captures int8 [n_captures, 2 N n_frames] -> (power uint64 [n_captures, N], band_power uint64 [K],
+        present uint8 [K]); blocking"""
+        cap = np.ascontiguousarray(captures, dtype=np.int8).reshape(self.W, 2 * self.N * int(n_frames))
+        k = self.n_bands
+        power = np.zeros((self.W, self.N), dtype=np.uint64)
+        bp, pr = np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.uint8)
+        check(self.L.hrfd_spec_process(self.h, _ptr(cap), int(n_frames), _ptr(power), _ptr(bp) if k else None,
+                                       _ptr(pr) if k else None), "hrfd_spec_process")
+        return power, bp, pr
+
+    def process_device(self, d_captures, capture_stride: int, n_frames: int, d_power, d_band_power=None, d_present=None,
+                       stream=None):
+        """device pointers (ints); asynchronous on stream (None = the handle's own)"""
+        check(self.L.hrfd_spec_process_device(self.h, _ptr(d_captures), int(capture_stride), int(n_frames), _ptr(d_power),
+                                              _ptr(d_band_power), _ptr(d_present), _ptr(stream)),
+              "hrfd_spec_process_device")
+
 
 class Engine:
     """Factory with the interface tests/goldencheck.py expects."""

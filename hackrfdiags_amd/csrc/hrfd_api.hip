@@ -164,11 +164,17 @@ extern "C" int hrfd_dbfs_table(int32_t *out)
   return HRFD_OK;
 }
 
+static int spec_named_table(const char *name, int16_t *out, int cap);   // hrfd_spec.hip: the tables built on the host
+
 extern "C" int hrfd_q15_table(const char *name, int16_t *out, int cap)
 {
   if (name == nullptr)
   {
     return 0;
+  }
+  if (strncmp(name, "SPEC_", 5) == 0)
+  {
+    return spec_named_table(name, out, cap);
   }
   for (const NamedTable &t : kNamedTables)
   {

@@ -456,11 +456,65 @@ int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pcm, uint32_t
                       uint64_t capture_stride, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * Spectrum bank: W wideband captures -> the power of every FFT bin, and the occupancy of K bands (no reference counterpart
+ * in the chain: it stands in for what the reference does by steering the radio, FrequencyScanner::run,
+ * FrequencyScanner.cc:378-400, and for the sweep tool beside it, hackrf-tools/hackrf_sweep.c:196-340 -- window, FFT, power
+ * per bin).  A capture is int8 IQ at R x 2.048 MS/s, the DDC's input; N = 2^L, L = 8..13.  A call takes n_frames frames
+ * (1..65536) of N samples (2 N bytes) from every capture, back to back, no overlap, and is a pure function of its input
+ * and the handle's settings: no history, no counter, nothing carried to the next call (unlike SignalTracker there is no
+ * tail: a band is present in a call or it is not).  Exact integer arithmetic, the same on every device
+ * (tests/spec_model.py restates it); complex values are (re, im) int16, shifts are arithmetic:
+ *   window    u = (x w[n] + 128) >> 8 per rail, w an int16 table of N entries, any values (-32768 included): |u| <= 16384
+ *             per rail.  Default: round(32767 * 0.5 * (1 - cos(2 pi n / N))) built on the host in double
+ *             (hrfd_q15_table "SPEC_HANN_8" .. "SPEC_HANN_13")
+ *   transform radix-2 decimation in frequency, L stages in place, natural order in, bit-reversed order out, halving in
+ *             every stage, rounded up in the even stages and down in the odd ones (r = 1 - (t mod 2); with one direction
+ *             in every stage the halvings' mean of a quarter LSB adds up to a hump of a few LSB around DC).  Stage t = 0..L-1 has span = N >> t, h = span / 2; for every i with (i mod span) < h, the pair
+ *             a = z[i], b = z[i + h], twiddle index k = (i mod span) (N / span), c = round(32767 cos(2 pi k / N)),
+ *             s = round(32767 sin(2 pi k / N)) (host, double; hrfd_q15_table "SPEC_COS_<L>" / "SPEC_SIN_<L>", N / 2 entries):
+ *               z[i]     = (a + b + r) >> 1                                 per component
+ *               d        = (a - b + r) >> 1                                 per component
+ *               z[i + h] = ((d_re c + d_im s + 2^14) >> 15, (d_im c - d_re s + 2^14) >> 15)
+ *             The result is X[k] = z[bitrev_L(k)] ~ DFT(u)[k] / N.  The complex magnitude never grows (<= 23170.5 after the
+ *             window), so every component stays within int16 and every product sum within int32.
+ *   power     p[k] = re^2 + im^2 (< 2^30) per frame; P[w][k] = the sum over the call's frames, uint64, in natural bin
+ *             order k = 0..N-1 (k >= N / 2 are the negative offsets; a bin is R * 2 048 000 / N Hz wide)
+ *   bands     K >= 0 bands (at most 65536), band -> (capture, first_bin, n_bins, threshold), 1 <= n_bins <= N, first_bin < N,
+ *             bins taken modulo N (a band may wrap through DC or through +-Fs/2), threshold <= 2^44 in power units per
+ *             frame (a band cannot hold more: N 2^31).  band_power[b] = the sum of P[capture] over the band's bins (uint64,
+ *             < 2^13 2^16 2^30), present[b] = band_power[b] >= threshold * n_frames (<= 2^44 2^16: inside uint64; larger
+ *             thresholds and frame counts are refused).  set_band with band == K appends, band < K replaces.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well); setters never wait for the
+ * device: the window and the bands a setter changed are copied to the device on the next call's stream, ahead of its
+ * launch.  Calls may use different streams: each launch is ordered on the device behind the handle's previous one.
+ *   hrfd_spec_process         host buffers: captures [W][2 N n_frames] -> power [W][N], band_power [K], present [K] (the
+ *                             last two may be NULL when K = 0); blocking
+ *   hrfd_spec_process_device  device buffers, capture rows capture_stride bytes apart (any byte address and stride),
+ *                             d_power 8-byte aligned; asynchronous on `stream` (a hipStream_t, NULL = the handle's own)
+ */
+typedef struct hrfd_spec hrfd_spec;
+#define HRFD_SPEC_MAX_FRAMES 65536u
+#define HRFD_SPEC_MAX_BANDS 65536u
+#define HRFD_SPEC_MAX_THRESHOLD (1ull << 44)
+int hrfd_spec_create(uint32_t n_captures, uint32_t decimation, uint32_t log2_n, int device, hrfd_spec **out);
+int hrfd_spec_destroy(hrfd_spec *s);
+int hrfd_spec_set_window(hrfd_spec *s, const int16_t *w);          /* N entries; NULL restores the default */
+int hrfd_spec_set_band(hrfd_spec *s, uint32_t band, uint32_t capture, uint32_t first_bin, uint32_t n_bins,
+                       uint64_t threshold);
+int hrfd_spec_clear_bands(hrfd_spec *s);                           /* K = 0 */
+int hrfd_spec_n_bands(hrfd_spec *s, uint32_t *k);
+int hrfd_spec_process(hrfd_spec *s, const int8_t *captures, uint32_t n_frames, uint64_t *power, uint64_t *band_power,
+                      uint8_t *present);
+int hrfd_spec_process_device(hrfd_spec *s, const int8_t *d_captures, uint64_t capture_stride, uint32_t n_frames,
+                             uint64_t *d_power, uint64_t *d_band_power, uint8_t *d_present, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",
  * "INTERP_HB1","INTERPSIG_S1", and the DDC bank's "DDC_COS" (4096 entries), "DDC_A2","DDC_A4","DDC_A8","DDC_B" (Q15 taps),
- * and the DUC bank's "DUC_A2","DUC_A4","DUC_A8" (Q15 taps).
+ * and the DUC bank's "DUC_A2","DUC_A4","DUC_A8" (Q15 taps), and the spectrum bank's "SPEC_HANN_<L>" (N entries),
+ * "SPEC_COS_<L>", "SPEC_SIN_<L>" (N / 2 entries), L = 8..13, built on the host.
  * Copies min(cap, count) entries (out may be NULL to ask for the count) and returns the count, 0 if unknown. */
 int hrfd_q15_table(const char *name, int16_t *out, int cap);
 /* host-built atan2 table [256][256] (float bits) and dBFS table [257] */
