@@ -161,6 +161,9 @@ def load() -> C.CDLL:
     L.hrfd_play_get_position.argtypes = [_vp, C.c_uint32, _u32p]
     L.hrfd_play_get_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp]
     L.hrfd_play_get.argtypes = [_vp, _vp, C.c_uint32]
+    if hasattr(L, "hrfd_debug_sincosf_eval"):              # (an older build named by HRFD_LIB has none)
+        L.hrfd_debug_sincosf_eval.argtypes = [C.c_int, C.c_int, _f32p, C.c_size_t, _f32p, _f32p]
+        L.hrfd_debug_sincosf_digest.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), _f32p]
     L.hrfd_nco_create.argtypes = [C.c_uint32, C.c_float, C.c_float, C.c_int, C.POINTER(_vp)]
     L.hrfd_nco_destroy.argtypes = [_vp]
     L.hrfd_nco_set_frequency.argtypes = [_vp, C.c_uint32, C.c_float]

@@ -854,5 +854,27 @@ def dbfs_table() -> np.ndarray:
     return out
 
 
+def debug_sincosf_eval(variant: int, form: int, x):
+    """(sin, cos) of every float of x by the device's restatement of glibc's sinf / cosf (hrfd_debug_sincosf_eval):
+    variant 0 / 1 without / with fused multiply-adds, form 0 the pair function, 1 the one-sided ones."""
+    x = np.ascontiguousarray(x, dtype=np.float32).ravel()
+    sn, cs = np.empty_like(x), np.empty_like(x)
+    f32p = C.POINTER(C.c_float)
+    check(_lib.load().hrfd_debug_sincosf_eval(int(variant), int(form), x.ctypes.data_as(f32p), x.size,
+                                              sn.ctypes.data_as(f32p), cs.ctypes.data_as(f32p)), "hrfd_debug_sincosf_eval")
+    return sn, cs
+
+
+def debug_sincosf_digest(variant: int, form: int, first_chunk: int, n_chunks: int, timed: bool = False):
+    """uint64 [n_chunks]: the device's digests of chunks of 2^20 float bit patterns (hrfd_debug_sincosf_digest);
+    timed: (digests, the kernel's milliseconds)"""
+    out = np.zeros(max(int(n_chunks), 0), dtype=np.uint64)
+    ms = C.c_float(0.0)
+    check(_lib.load().hrfd_debug_sincosf_digest(int(variant), int(form), int(first_chunk), int(n_chunks),
+                                                out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ms) if timed else None),
+          "hrfd_debug_sincosf_digest")
+    return (out, float(ms.value)) if timed else out
+
+
 def device_count() -> int:
     return int(_lib.load().hrfd_device_count())

@@ -108,6 +108,93 @@ static int atan_eval(hrfd_rx *h, float *out65536, bool tab)
   return HRFD_OK;
 }
 
+// read-only: the device's restatement of glibc's sinf / cosf (glibc_sincosf*, hrfd_tx_kernels.hip), on the current
+// device.  variant 0 / 1 selects the template (without / with fused multiply-adds) whatever libm the host has; form 0 is
+// the pair function of every product caller, 1 glibc_sinf and glibc_cosf called separately.  Host pointers.
+static int sincosf_args(const char *who, int variant, int form)
+{
+  if ((variant != 0 && variant != 1) || (form != 0 && form != 1))
+  {
+    return fail(HRFD_EINVAL, "%s: variant 0 | 1, form 0 | 1", who);
+  }
+  return HRFD_OK;
+}
+extern "C" int hrfd_debug_sincosf_eval(int variant, int form, const float *x, size_t n, float *sn, float *cs)
+{
+  int rc = sincosf_args("hrfd_debug_sincosf_eval", variant, form);
+  if (rc != HRFD_OK) return rc;
+  if (x == nullptr || sn == nullptr || cs == nullptr || n == 0 || n > ((size_t)1 << 28))
+  {
+    return fail(HRFD_EINVAL, "hrfd_debug_sincosf_eval: NULL, or n not in 1 .. 2^28");
+  }
+  if (hrfd_device_count() <= 0)
+  {
+    return fail(HRFD_ENODEV, "hrfd_debug_sincosf_eval: no HIP device visible");
+  }
+  float *d = nullptr;                                      // [3][n]: x, sin, cos
+  HIP_TRY(hipMalloc((void **)&d, 3 * n * sizeof(float)));
+  hipError_t e = hipMemcpy(d, x, n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+  {
+    hipLaunchKernelGGL(k_sincosf_eval, dim3((uint32_t)((n + kSinCosThreads - 1) / kSinCosThreads)), dim3(kSinCosThreads), 0, 0,
+                       d, n, variant, form, d + n, d + 2 * n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(sn, d + n, n * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(cs, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess)
+  {
+    return fail(HRFD_ENODEV, "hrfd_debug_sincosf_eval: %s", hipGetErrorString(e));
+  }
+  return HRFD_OK;
+}
+// out[k]: the digest of chunk first_chunk + k (2^20 consecutive float bit patterns, k_sincosf_digest); *kernel_ms (may be
+// NULL): the kernel's time between two HIP events
+extern "C" int hrfd_debug_sincosf_digest(int variant, int form, uint32_t first_chunk, uint32_t n_chunks, uint64_t *out,
+                                         float *kernel_ms)
+{
+  int rc = sincosf_args("hrfd_debug_sincosf_digest", variant, form);
+  if (rc != HRFD_OK) return rc;
+  if (out == nullptr || n_chunks == 0 || first_chunk > 4095u || n_chunks > 4096u - first_chunk)
+  {
+    return fail(HRFD_EINVAL, "hrfd_debug_sincosf_digest: NULL, or chunks that leave 0 .. 4095");
+  }
+  if (hrfd_device_count() <= 0)
+  {
+    return fail(HRFD_ENODEV, "hrfd_debug_sincosf_digest: no HIP device visible");
+  }
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the digest is 64 bits");
+  unsigned long long *d = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIP_TRY(hipMalloc((void **)&d, n_chunks * sizeof(uint64_t)));
+  hipError_t e = hipSuccess;
+  if (kernel_ms != nullptr)
+  {
+    e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], 0);
+  }
+  if (e == hipSuccess)
+  {
+    hipLaunchKernelGGL(k_sincosf_digest, dim3(n_chunks), dim3(kSinCosThreads), 0, 0, first_chunk, variant, form, d);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && kernel_ms != nullptr) e = hipEventRecord(ev[1], 0);
+  if (e == hipSuccess) e = hipMemcpy(out, d, n_chunks * sizeof(uint64_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && kernel_ms != nullptr) e = hipEventElapsedTime(kernel_ms, ev[0], ev[1]);
+  for (hipEvent_t v : ev)
+  {
+    if (v) (void)hipEventDestroy(v);
+  }
+  (void)hipFree(d);
+  if (e != hipSuccess)
+  {
+    return fail(HRFD_ENODEV, "hrfd_debug_sincosf_digest: %s", hipGetErrorString(e));
+  }
+  return HRFD_OK;
+}
+
 // test hook: -1 automatic (arithmetic atan2 when its corrections fit), 0 force the table gather,
 // 1 require the arithmetic kernel (fails if the corrections did not fit)
 extern "C" int hrfd_rx_debug_set_atan(hrfd_rx *h, int mode)

@@ -848,6 +848,17 @@ static int nco_free(hrfd_nco *h)
   return HRFD_OK;
 }
 
+// PhaseAccumulator.cc:41 / :105: the step is a double expression stored to float.  The wrap loops of k_nco (and of the
+// reference) subtract 2 pi from a FLOAT accumulator: from about 2^27 rad that no longer changes the value and the loop
+// never ends, and a NaN or an infinity never passes either compare's way out.  So a step that is not finite or reaches 2^24
+// rad (three binades below, many orders of magnitude above every frequency the reference's callers use) is refused on the
+// host, before anything is launched.
+static bool nco_step(float sample_rate, float frequency, float *step)
+{
+  *step = (float)((2 * M_PI * frequency) / sample_rate);
+  return std::isfinite(*step) && fabsf(*step) < 16777216.0f;
+}
+
 extern "C" int hrfd_nco_create(uint32_t n_channels, float sample_rate, float frequency, int device,
                                hrfd_nco **out)
 {
@@ -856,6 +867,11 @@ extern "C" int hrfd_nco_create(uint32_t n_channels, float sample_rate, float fre
     return fail(HRFD_EINVAL, "hrfd_nco_create: bad arguments");
   }
   *out = nullptr;
+  float step0;
+  if (!nco_step(sample_rate, frequency, &step0))
+  {
+    return fail(HRFD_EINVAL, "hrfd_nco_create: the phase step 2 pi f / fs is not finite or is 2^24 rad or more");
+  }
   if (hrfd_device_count() <= 0)
   {
     return fail(HRFD_ENODEV, "hrfd_nco_create: no HIP device visible (this library has no CPU path)");
@@ -870,7 +886,7 @@ extern "C" int hrfd_nco_create(uint32_t n_channels, float sample_rate, float fre
   h->n_channels = n_channels;
   h->sample_rate = sample_rate;
   // PhaseAccumulator.cc:41: double expression stored to float
-  h->h_step.assign(n_channels, (float)((2 * M_PI * frequency) / sample_rate));
+  h->h_step.assign(n_channels, step0);
   // Nco.cc:50-61: tables from a float angle accumulated by float increments; sin/cos
   // of a float argument are sinf/cosf under the C++ overloads -> host libm
   std::vector<float> st(16384), ct(16384);
@@ -910,7 +926,11 @@ extern "C" int hrfd_nco_set_frequency(hrfd_nco *h, uint32_t channel, float frequ
   {
     return fail(HRFD_EINVAL, "hrfd_nco_set_frequency: bad handle or channel");
   }
-  const float step = (float)((2 * M_PI * frequency) / h->sample_rate);   // PhaseAccumulator.cc:105
+  float step;                                              // PhaseAccumulator.cc:105
+  if (!nco_step(h->sample_rate, frequency, &step))
+  {
+    return fail(HRFD_EINVAL, "hrfd_nco_set_frequency: the phase step 2 pi f / fs is not finite or is 2^24 rad or more (nothing changed)");
+  }
   for (uint32_t c = 0; c < h->n_channels; c++)
   {
     if (channel == HRFD_ALL_CHANNELS || channel == c)

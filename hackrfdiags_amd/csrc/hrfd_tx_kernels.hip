@@ -213,10 +213,16 @@ __device__ __forceinline__ void wg_loop(const int tid, F &&body)
 // that cosf / sinf (Nco.cc:186-199, signals/pm.cc:41-53, fm.cc:44-77).  glibc's are the ARM
 // optimized-routines algorithm (sysdeps/ieee754/flt-32/s_sinf.c, s_cosf.c, sincosf.h, s_sincosf_data.c): reduction by
 // pi/2 in double (n = round(x * 2/pi) by an integer trick, x - n * pi/2), then one of two double polynomials, rounded
-// to float once -- deterministic, so it can be the device's arithmetic as well: tools/proofs/sincosf_glibc.c checks
-// this restatement against the host's libm on EVERY float with |x| < 120 (2.2e9 values): 0 mismatches with the
-// fused multiply-adds of the -mfma build that x86-64 glibc dispatches to on an FMA-capable CPU, 34 (all at |x| > 17)
-// without them.  FMA: which of the two the host's libm is -- probed by the host (libm_variant, hrfd_api_tx.hip).
+// to float once -- deterministic, so it can be the device's arithmetic as well.  The evidence has two halves:
+//   * the restatement in plain C (oracle/sincosf_model.h) against the host's libm on EVERY float with |x| < 120 (2.2e9
+//     values; tools/proofs/sincosf_glibc.c, and as a test tests/test_sincos_model.py): 0 mismatches with the fused
+//     multiply-adds of the -mfma build that x86-64 glibc dispatches to on an FMA-capable CPU, 34 (all at |x| > 17)
+//     without them;
+//   * what THIS file compiles to for the device against that restatement, again on every float of the range, in BOTH
+//     variants and both forms (the pair and the one-sided functions): tests/test_gpu_sincos.py, through k_sincosf_digest
+//     and k_sincosf_eval below (hrfd_debug_sincosf_digest / _eval) -- the host's probe picks one variant per machine, the
+//     test runs both.
+// FMA: which of the two the host's libm is -- probed by the host (libm_variant, hrfd_api_tx.hip).
 // Outside the restated range (|x| >= 120, NaN) the double-precision cos / sin rounded to float stand in (never reached:
 // every caller wraps its phase into (-2 pi, 2 pi)).
 // Provenance: the eight polynomial coefficients and the reduction constants below are the published values of glibc
@@ -352,6 +358,80 @@ __device__ __forceinline__ float glibc_sinf(float y, int fma_variant)
 __device__ __forceinline__ float glibc_cosf(float y, int fma_variant)
 {
   return fma_variant ? glibc_sincosf_v<true, true>(y) : glibc_sincosf_v<false, true>(y);
+}
+
+// ---- read-only introspection of the above (include/hrfd_debug.h: hrfd_debug_sincosf_eval / _digest) -----------------
+// form 0: the pair function every product caller uses; 1: glibc_sinf and glibc_cosf called separately
+__device__ __forceinline__ void sincosf_form(float y, int variant, int form, float &sn, float &cs)
+{
+  if (form == 0)
+  {
+    glibc_sincosf(y, variant, sn, cs);
+  }
+  else
+  {
+    sn = glibc_sinf(y, variant);
+    cs = glibc_cosf(y, variant);
+  }
+}
+constexpr int kSinCosThreads = 256;
+__global__ __launch_bounds__(kSinCosThreads) void k_sincosf_eval(const float *__restrict__ x, size_t n, int variant, int form,
+                                                                 float *__restrict__ sn, float *__restrict__ cs)
+{
+  const size_t i = (size_t)blockIdx.x * kSinCosThreads + threadIdx.x;
+  if (i < n)
+  {
+    float s, c;
+    sincosf_form(x[i], variant, form, s, c);
+    sn[i] = s;
+    cs[i] = c;
+  }
+}
+// (the same mix as oracle/hrfd_oracle.c: sincosf_mix -- the pattern goes in, so two neighbours with swapped results do
+//  not cancel in the order-independent sum)
+__device__ __forceinline__ unsigned long long sincosf_mix(uint32_t u, uint32_t s, uint32_t c)
+{
+  unsigned long long z = (((unsigned long long)s << 32) | c) + (unsigned long long)u * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// One workgroup per chunk of 2^20 consecutive float bit patterns (chunk k: k << 20 ...): out[blockIdx.x] = the wrapping
+// 64-bit sum of sincosf_mix(u, bits(sin), bits(cos)) over the chunk.  Each lane sums 4096 patterns in a register, the
+// wave by shuffles, the four waves through LDS; lane 0 stores the chunk's value once.
+__global__ __launch_bounds__(kSinCosThreads) void k_sincosf_digest(uint32_t first_chunk, int variant, int form,
+                                                                   unsigned long long *__restrict__ out)
+{
+  __shared__ unsigned long long part[kSinCosThreads / 64];
+  const uint32_t base = (first_chunk + blockIdx.x) << 20;
+  unsigned long long acc = 0;
+  for (uint32_t j = threadIdx.x; j < (1u << 20); j += kSinCosThreads)
+  {
+    const uint32_t u = base + j;
+    float s, c;
+    sincosf_form(__builtin_bit_cast(float, u), variant, form, s, c);
+    acc += sincosf_mix(u, __builtin_bit_cast(uint32_t, s), __builtin_bit_cast(uint32_t, c));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+  {
+    acc += __shfl_down(acc, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0)
+  {
+    part[threadIdx.x >> 6] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    unsigned long long sum = 0;
+#pragma unroll
+    for (int w = 0; w < kSinCosThreads / 64; w++)
+    {
+      sum += part[w];
+    }
+    out[blockIdx.x] = sum;
+  }
 }
 
 // Stages 6, 7, 8 of the cascade (HB3, HB2, HB1: x8) for ONE 256 kS/s sample j of both rails, in registers: v[rail][0] =

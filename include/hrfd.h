@@ -338,11 +338,16 @@ int hrfd_play_get(hrfd_play *h, int8_t *out, uint32_t bytes_per_channel);
  * i_out/q_out are [n_channels][count] float host buffers.
  * Accuracy: the phase sequence is the reference's bit for bit (float accumulate, double-compare
  * wrap).  fast != 0 (Nco::runFast): the values are the host-built table's -- bit-exact.
- * fast == 0 (Nco::run): the reference calls libm sinf/cosf; the device evaluates cos/sin of the
- * same phase in double and rounds to float, so a value may differ from glibc's by one ulp (the
- * float-trig tolerance the north star allows; tests/test_gpu_tx_nco.py states it).  The same holds
- * for what is built on Nco::run: the FM modulator and the pm / fm generators (int8 IQ within
- * +-1 LSB, see hrfd_mod_create).
+ * fast == 0 (Nco::run): the reference calls libm sinf/cosf; the device restates glibc's algorithm
+ * (the build hrfd_libm_variant() names) and gives the same floats bit for bit -- the device code is
+ * compared with the restatement in C on every float with |x| < 120, in both variants
+ * (tests/test_gpu_sincos.py), and that restatement with the host's libm (tests/test_sincos_model.py).
+ * The same holds for what is built on Nco::run: the FM modulator and the pm / fm generators.
+ *
+ * hrfd_nco_create and hrfd_nco_set_frequency REFUSE (HRFD_EINVAL, nothing changed, nothing launched) a
+ * frequency whose phase step (float)(2 pi f / fs) is not finite or is 2^24 rad or more in magnitude:
+ * the wrap loops subtract 2 pi from a float, which from about 2^27 rad no longer changes it, so the
+ * kernel -- like the reference's thread in the same place -- would never return.
  */
 typedef struct hrfd_nco hrfd_nco;
 int hrfd_nco_create(uint32_t n_channels, float sample_rate, float frequency, int device,

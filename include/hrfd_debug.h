@@ -41,6 +41,20 @@ int hrfd_rx_debug_chk(hrfd_rx *h, float *pub, float *spec, uint32_t n);
  * its state in RagState since; *launches: launches so far that ran on k_rx_ragged (hrfd_rx_ragged.hip) */
 int hrfd_rx_debug_ragged(hrfd_rx *h, int *offgrid, unsigned long long *launches);
 
+/* the device's restatement of glibc's sinf / cosf (hrfd_tx_kernels.hip: glibc_sincosf*), evaluated on the current
+ * device; host pointers.  variant 0 / 1: without / with fused multiply-adds -- selects the template, not what the host's
+ * libm was probed to be (hrfd_libm_variant()); form 0: the pair function every product caller uses, 1: the one-sided
+ * sinf and cosf called separately.
+ *   eval  : sn[i], cs[i] = sin, cos of x[i], n in 1 .. 2^28.
+ *   digest: a chunk is 2^20 consecutive float bit patterns u (chunk k: u >> 20 == k); out[k] = the wrapping 64-bit sum
+ *           over chunk first_chunk + k of mix(u, bits(sin), bits(cos)), mix(u, s, c) = splitmix64's finaliser of
+ *           ((s << 32) | c) + u * 0x9E3779B97F4A7C15 -- the same sum oracle/hrfd_oracle.c makes of the host's libm and of
+ *           the restatement in C (orc_sincosf_digest).  The restated range |x| < 120 is chunks 0 .. 1070 and
+ *           2048 .. 3118; chunk ranges that leave 0 .. 4095 are refused (HRFD_EINVAL).  *kernel_ms (may be NULL): the
+ *           kernel's time.  tests/test_gpu_sincos.py: every float of the range, both variants, both forms. */
+int hrfd_debug_sincosf_eval(int variant, int form, const float *x, size_t n, float *sn, float *cs);
+int hrfd_debug_sincosf_digest(int variant, int form, uint32_t first_chunk, uint32_t n_chunks, uint64_t *out, float *kernel_ms);
+
 /* two plain stream kernels -- kind 0 reads `bytes` of d_buf (d_sink: one dword that is never written, may be NULL),
  * kind 1 overwrites them; bytes a multiple of 256 KiB; asynchronous on `stream`.  bench.py times them in the same run
  * as the measured denominators beside the 8 TB/s spec peak (`measured_stream_read_GBps` / `_write_GBps`). */

@@ -23,6 +23,7 @@
 #define _GNU_SOURCE
 #include "hrfd_oracle.h"
 #include "hrfd_oracle_tables.h"
+#include "sincosf_model.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -1491,6 +1492,91 @@ void orc_nco_tables(orc_nco *h, float *sin_out, float *cos_out)
 {
   memcpy(sin_out, h->sin_t, sizeof(h->sin_t));
   memcpy(cos_out, h->cos_t, sizeof(h->cos_t));
+}
+
+/* the phase sequence alone: advances the accumulator like orc_nco_run and records, per sample, the phase handed out
+ * (before the step) and how many turns the two wrap loops of PhaseAccumulator::run took after the step */
+void orc_nco_phases(orc_nco *h, uint32_t count, float *phase_out, uint32_t *turns_out)
+{
+  for (uint32_t k = 0; k < count; k++)
+  {
+    uint32_t turns = 0;
+    phase_out[k] = h->acc;
+    h->acc += h->step;
+    while (h->acc > M_PI)
+    {
+      h->acc = (float)((double)h->acc - (2 * M_PI));
+      turns++;
+    }
+    while (h->acc < (-M_PI))
+    {
+      h->acc = (float)((double)h->acc + (2 * M_PI));
+      turns++;
+    }
+    turns_out[k] = turns;
+  }
+}
+
+/* ------------------------------------------------------------------ sinf / cosf: the host's libm and the restatement
+ * source 0 / 1: glibc's algorithm without / with fma() (sincosf_model.h), 2: this host's sinf / cosf.
+ * A chunk is 2^20 consecutive float bit patterns; its digest the wrapping 64-bit sum of sincosf_mix over them -- the same
+ * mix as the device's (k_sincosf_digest, hrfd_tx_kernels.hip). */
+static inline uint64_t sincosf_mix(uint32_t u, uint32_t s, uint32_t c)
+{
+  uint64_t z = (((uint64_t)s << 32) | c) + (uint64_t)u * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+static inline void sincosf_source(int source, float x, float *sn, float *cs)
+{
+  if (source == 2)
+  {
+    *sn = sinf(x);
+    *cs = cosf(x);
+  }
+  else
+  {
+    *sn = hrfd_sinf(source, x);
+    *cs = hrfd_cosf(source, x);
+  }
+}
+
+int orc_sincosf_eval(int source, const float *x, size_t n, float *sn, float *cs)
+{
+  if (source < 0 || source > 2)
+  {
+    return -1;
+  }
+  for (size_t i = 0; i < n; i++)
+  {
+    sincosf_source(source, x[i], &sn[i], &cs[i]);
+  }
+  return 0;
+}
+
+int orc_sincosf_digest(int source, uint32_t first_chunk, uint32_t n_chunks, uint64_t *out)
+{
+  if (source < 0 || source > 2 || first_chunk > 4095 || n_chunks > 4096 - first_chunk)
+  {
+    return -1;
+  }
+  for (uint32_t k = 0; k < n_chunks; k++)
+  {
+    const uint32_t base = (first_chunk + k) << 20;
+    uint64_t acc = 0;
+    for (uint32_t j = 0; j < (1u << 20); j++)
+    {
+      const uint32_t u = base + j;
+      float x, sn, cs;
+      memcpy(&x, &u, 4);
+      sincosf_source(source, x, &sn, &cs);
+      acc += sincosf_mix(u, scm_asuint(sn), scm_asuint(cs));
+    }
+    out[k] = acc;
+  }
+  return 0;
 }
 
 /* ------------------------------------------------------------------ primitives */

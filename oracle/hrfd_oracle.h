@@ -13,6 +13,7 @@
 #ifndef HRFD_ORACLE_H
 #define HRFD_ORACLE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -104,6 +105,16 @@ void orc_nco_set_frequency(orc_nco *h, float frequency);
 void orc_nco_reset(orc_nco *h);
 void orc_nco_run(orc_nco *h, int fast, uint32_t count, float *i_out, float *q_out);
 void orc_nco_tables(orc_nco *h, float *sin_out, float *cos_out);
+/* the phase sequence of `count` samples (advances the state like orc_nco_run) and the turns of the wrap loops per step */
+void orc_nco_phases(orc_nco *h, uint32_t count, float *phase_out, uint32_t *turns_out);
+
+/* ---- sinf / cosf.  source 0 / 1: glibc 2.35's algorithm restated without / with fma() (sincosf_model.h; |x| < 120,
+ * outside it the double sin / cos rounded), 2: the host's libm.  eval: sn[i], cs[i] of x[i].  digest: out[k] = the
+ * wrapping 64-bit sum, over the 2^20 float bit patterns u of chunk first_chunk + k (u >> 20 == chunk), of a mix of
+ * (u, bits(sin), bits(cos)): order-independent, and the same mix as hrfd_debug_sincosf_digest on the device.  |x| < 120
+ * is chunks 0..1070 and 2048..3118.  Both return 0, or -1 for an unknown source or a chunk range that leaves 0..4095. */
+int orc_sincosf_eval(int source, const float *x, size_t n, float *sn, float *cs);
+int orc_sincosf_digest(int source, uint32_t first_chunk, uint32_t n_chunks, uint64_t *out);
 
 /* ---- primitives and tables */
 void orc_quantise(const float *coeffs, int count, int16_t *out);

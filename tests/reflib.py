@@ -35,8 +35,9 @@ def iq256_capacity(block_bytes: int) -> int:
 
 
 def build_oracle():
+    srcs = ("hrfd_oracle.c", "hrfd_oracle.h", "hrfd_oracle_tables.h", "sincosf_model.h")
     if not os.path.exists(ORACLE_SO) or (
-            os.path.getmtime(ORACLE_SO) < os.path.getmtime(os.path.join(ORACLE_DIR, "hrfd_oracle.c"))):
+            os.path.getmtime(ORACLE_SO) < max(os.path.getmtime(os.path.join(ORACLE_DIR, f)) for f in srcs)):
         subprocess.check_call(["make", "-C", ORACLE_DIR, "oracle"], stdout=subprocess.DEVNULL)
 
 
@@ -401,6 +402,15 @@ class _Nco:
         c = np.zeros(16384, dtype=np.float32)
         getattr(self.lib, f"{self.px}_nco_tables")(self.h, _p(s, _f32p), _p(c, _f32p))
         return s, c
+
+    def phases(self, n):
+        """(oracle only) advances the state like run(n); returns the phases handed out and the turns the wrap loops took"""
+        fn = self.lib.orc_nco_phases
+        fn.argtypes = [C.c_void_p, C.c_uint32, _f32p, _u32p]
+        p = np.zeros(n, dtype=np.float32)
+        t = np.zeros(n, dtype=np.uint32)
+        fn(self.h, n, _p(p, _f32p), _p(t, _u32p))
+        return p, t
 
 
 class Ref:

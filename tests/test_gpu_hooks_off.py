@@ -40,6 +40,8 @@ GROUPS = [
     ("ddc_bank", "test_gpu_ddc", "", 36),
     ("ddc_edges", "test_gpu_ddc_edges", "", 36),
     ("squelch_sweep", "test_gpu_squelch_sweep", "", 40),
+    ("sincos_every_float", "test_gpu_sincos", "", 8),
+    ("nco_sweep", "test_gpu_nco_sweep", "", 11),
 ]
 
 

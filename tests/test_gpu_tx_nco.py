@@ -92,8 +92,11 @@ def test_nco_fast_and_run_are_bit_exact(oracle):
         g.set_frequency(f / 3); o.set_frequency(f / 3)
         ia, qa = g.run(2000, fast=False)
         ib, qb = o.run(2000, False)
-        # Nco::run calls libm sinf/cosf (Nco.cc:186-199): glibc's algorithm restated on the device (round 5: glibc_sinf /
-        # glibc_cosf, checked against the host's libm on every float by tools/proofs/sincosf_glibc.c) -- no tolerance
+        # Nco::run calls libm sinf/cosf (Nco.cc:186-199): glibc's algorithm restated on the device (round 5: glibc_sincosf).
+        # The DEVICE code is held to the restatement in C on every float with |x| < 120, in both variants and both forms,
+        # by tests/test_gpu_sincos.py, and that restatement to the host's libm by tests/test_sincos_model.py (the
+        # statement of tools/proofs/sincosf_glibc.c); k_nco's banks, wraps and setters by tests/test_gpu_nco_sweep.py --
+        # no tolerance
         assert (bits(ia) == bits(ib)).all() and (bits(qa) == bits(qb)).all()
         g.reset(); o.reset()
         ia, _ = g.run(10, True); ib, _ = o.run(10, True)

@@ -11,6 +11,10 @@
  * two can differ where a product-sum is contracted.  Both variants are evaluated here (FMA = 0 / 1) and the program
  * says which one -- or both -- equals the host's sinf / cosf everywhere.
  *
+ * The restatement itself lives in oracle/sincosf_model.h: the CPU checker evaluates the same text
+ * (orc_sincosf_eval / orc_sincosf_digest), tests/test_sincos_model.py makes this program's statement a test and
+ * tests/test_gpu_sincos.py holds the DEVICE's restatement to it on every float of the range.
+ *
  * build: gcc -O2 -ffp-contract=off -fopenmp -o sincosf_glibc sincosf_glibc.c -lm      run: ./sincosf_glibc
  */
 #include <math.h>
@@ -18,113 +22,9 @@
 #include <stdio.h>
 #include <string.h>
 
-typedef struct
-{
-  double sign[4];
-  double hpi_inv, hpi, c0, c1, c2, c3, c4, s1, s2, s3;
-} sincos_t;
+#include "../../oracle/sincosf_model.h"                    /* the restatement: hrfd_sinf / hrfd_cosf (FMA, x) */
 
-static const sincos_t T[2] = {
-    {{1.0, -1.0, -1.0, 1.0},
-     0x1.45F306DC9C883p+23,
-     0x1.921FB54442D18p0,
-     0x1p0,
-     -0x1.ffffffd0c621cp-2,
-     0x1.55553e1068f19p-5,
-     -0x1.6c087e89a359dp-10,
-     0x1.99343027bf8c3p-16,
-     -0x1.555545995a603p-3,
-     0x1.1107605230bc4p-7,
-     -0x1.994eb3774cf24p-13},
-    {{1.0, -1.0, -1.0, 1.0},
-     0x1.45F306DC9C883p+23,
-     0x1.921FB54442D18p0,
-     -0x1p0,
-     0x1.ffffffd0c621cp-2,
-     -0x1.55553e1068f19p-5,
-     0x1.6c087e89a359dp-10,
-     -0x1.99343027bf8c3p-16,
-     -0x1.555545995a603p-3,
-     0x1.1107605230bc4p-7,
-     -0x1.994eb3774cf24p-13}};
-
-static inline uint32_t asuint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-static inline uint32_t abstop12(float x) { return (asuint(x) >> 20) & 0x7ff; }
-
-#define MA(FMA, a, b, c) ((FMA) ? fma((a), (b), (c)) : ((a) * (b) + (c)))
-
-/* sinf_poly: n even -> sine polynomial of x, odd -> cosine polynomial */
-static inline float poly(int FMA, double x, double x2, const sincos_t *p, int n)
-{
-  if ((n & 1) == 0)
-  {
-    const double x3 = x * x2;
-    const double s1 = MA(FMA, x2, p->s3, p->s2);
-    const double x7 = x3 * x2;
-    const double s = MA(FMA, x3, p->s1, x);
-    return (float)MA(FMA, x7, s1, s);
-  }
-  const double x4 = x2 * x2;
-  const double c2 = MA(FMA, x2, p->c4, p->c3);
-  const double c1 = MA(FMA, x2, p->c1, p->c0);
-  const double x6 = x4 * x2;
-  const double c = MA(FMA, x4, p->c2, c1);
-  return (float)MA(FMA, x6, c2, c);
-}
-
-static inline double reduce_fast(int FMA, double x, const sincos_t *p, int *np)
-{
-  const double r = x * p->hpi_inv;
-  const int n = ((int32_t)r + 0x800000) >> 24;
-  *np = n;
-  return FMA ? fma(-(double)n, p->hpi, x) : x - n * p->hpi;
-}
-
-float hrfd_sinf(int FMA, float y)
-{
-  double x = y;
-  const sincos_t *p = &T[0];
-  if (abstop12(y) < abstop12(0x1.921FB6p-1f))             /* |y| < pi/4 */
-  {
-    const double s = x * x;
-    if (abstop12(y) < abstop12(0x1p-12f))
-    {
-      return y;
-    }
-    return poly(FMA, x, s, p, 0);
-  }
-  int n;
-  x = reduce_fast(FMA, x, p, &n);
-  const double s = p->sign[n & 3];
-  if (n & 2)
-  {
-    p = &T[1];
-  }
-  return poly(FMA, x * s, x * x, p, n);
-}
-
-float hrfd_cosf(int FMA, float y)
-{
-  double x = y;
-  const sincos_t *p = &T[0];
-  if (abstop12(y) < abstop12(0x1.921FB6p-1f))
-  {
-    const double x2 = x * x;
-    if (abstop12(y) < abstop12(0x1p-12f))
-    {
-      return 1.0f;
-    }
-    return poly(FMA, x, x2, p, 1);
-  }
-  int n;
-  x = reduce_fast(FMA, x, p, &n);
-  const double s = p->sign[n & 3];
-  if (n & 2)
-  {
-    p = &T[1];
-  }
-  return poly(FMA, x * s, x * x, p, n ^ 1);
-}
+static inline uint32_t asuint(float f) { return scm_asuint(f); }
 
 int main(void)
 {
