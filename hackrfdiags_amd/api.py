@@ -515,30 +515,58 @@ def ddc_step(offset_hz: float, decimation: int) -> int:
     return int(round(float(offset_hz) / (int(decimation) * DDC_FS_OUT) * 2.0 ** 32)) & 0xFFFFFFFF
 
 
-class Ddc:
-    """A bank of digital down-converters (hrfd_ddc_*): n_captures wideband int8 IQ captures at decimation x 2.048 MS/s
-    in, n_channels int8 IQ streams at 2.048 MS/s out, the input Rx takes."""
+class _Bank:
+    """What Ddc, Duc and Spectrum share: the handle of hrfd_<_prefix>_create and its release."""
+    _prefix = ""
 
-    def __init__(self, n_captures: int, n_channels: int, decimation: int, device: int = -1):
+    def _create(self, *args):
         self.L = _lib.load()
-        self.W, self.n, self.R = int(n_captures), int(n_channels), int(decimation)
         h = C.c_void_p()
-        check(self.L.hrfd_ddc_create(self.W, self.n, self.R, device, C.byref(h)), "hrfd_ddc_create")
+        check(self._fn("create")(*args, C.byref(h)), f"hrfd_{self._prefix}_create")
         self.h = h
+
+    def _fn(self, name):
+        return getattr(self.L, f"hrfd_{self._prefix}_{name}")
+
+    def _call(self, name, *args):
+        check(self._fn(name)(self.h, *args), f"hrfd_{self._prefix}_{name}")
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.hrfd_ddc_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = None
 
     __del__ = close
 
+
+class _TunedBank(_Bank):
+    """The calls of Ddc and Duc that differ in the prefix only."""
+
     def reset(self):
-        check(self.L.hrfd_ddc_reset(self.h), "hrfd_ddc_reset")
+        self._call("reset")
 
     def set_step(self, channel: int, capture: int, step: int):
-        check(self.L.hrfd_ddc_set_tuning(self.h, int(channel), int(capture), int(step) & 0xFFFFFFFF),
-              "hrfd_ddc_set_tuning")
+        self._call("set_tuning", int(channel), int(capture), int(step) & 0xFFFFFFFF)
+
+    def _set_filter(self, stage: int, taps):
+        t = np.ascontiguousarray(taps, dtype=np.int16)
+        self._call("set_filter", int(stage), t.ctypes.data_as(C.POINTER(C.c_int16)), t.size)
+
+    def phase(self, channel: int) -> int:
+        v = C.c_uint32(0)
+        self._call("get_phase", int(channel), C.byref(v))
+        return int(v.value)
+
+
+class Ddc(_TunedBank):
+    """A bank of digital down-converters (hrfd_ddc_*): n_captures wideband int8 IQ captures at decimation x 2.048 MS/s
+    in, n_channels int8 IQ streams at 2.048 MS/s out, the input Rx takes."""
+
+    _prefix = "ddc"
+
+    def __init__(self, n_captures: int, n_channels: int, decimation: int, device: int = -1):
+        self.W, self.n, self.R = int(n_captures), int(n_channels), int(decimation)
+        self._create(self.W, self.n, self.R, device)
 
     def tune(self, channel: int, capture: int, station_offset_hz: float):
         """put the station at station_offset_hz from the capture's centre where Rx expects it (64 kHz below the
@@ -554,14 +582,7 @@ class Ddc:
 
     def set_filter(self, stage: int, taps):
         """stage 0 = A (decimating), 1 = B (channel); empty taps = bypass"""
-        t = np.ascontiguousarray(taps, dtype=np.int16)
-        check(self.L.hrfd_ddc_set_filter(self.h, int(stage), t.ctypes.data_as(C.POINTER(C.c_int16)), t.size),
-              "hrfd_ddc_set_filter")
-
-    def phase(self, channel: int) -> int:
-        v = C.c_uint32(0)
-        check(self.L.hrfd_ddc_get_phase(self.h, int(channel), C.byref(v)), "hrfd_ddc_get_phase")
-        return int(v.value)
+        self._set_filter(stage, taps)
 
     def process(self, captures: np.ndarray, out_bytes: int) -> np.ndarray:
         """captures int8 [n_captures, decimation * out_bytes] -> int8 [n_channels, out_bytes]; blocking"""
@@ -591,30 +612,15 @@ def duc_step(offset_hz: float, interpolation: int) -> int:
     return ddc_step(offset_hz, interpolation)
 
 
-class Duc:
+class Duc(_TunedBank):
     """A bank of digital up-converters (hrfd_duc_*): n_channels int8 IQ streams at 2.048 MS/s (what Mod writes) in,
     n_captures wideband int8 IQ captures at interpolation x 2.048 MS/s out, each the sum of the channels tuned to it."""
 
+    _prefix = "duc"
+
     def __init__(self, n_captures: int, n_channels: int, interpolation: int, device: int = -1):
-        self.L = _lib.load()
         self.W, self.n, self.R = int(n_captures), int(n_channels), int(interpolation)
-        h = C.c_void_p()
-        check(self.L.hrfd_duc_create(self.W, self.n, self.R, device, C.byref(h)), "hrfd_duc_create")
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hrfd_duc_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def reset(self):
-        check(self.L.hrfd_duc_reset(self.h), "hrfd_duc_reset")
-
-    def set_step(self, channel: int, capture: int, step: int):
-        check(self.L.hrfd_duc_set_tuning(self.h, int(channel), int(capture), int(step) & 0xFFFFFFFF),
-              "hrfd_duc_set_tuning")
+        self._create(self.W, self.n, self.R, device)
 
     def tune(self, channel: int, capture: int, offset_hz: float):
         """put the channel's DC (the station, as the modulators write it) at offset_hz from the capture's centre"""
@@ -631,14 +637,7 @@ class Duc:
 
     def set_filter(self, stage: int, taps):
         """stage 0 = A (interpolating), 1 = B (channel); empty taps = bypass"""
-        t = np.ascontiguousarray(taps, dtype=np.int16)
-        check(self.L.hrfd_duc_set_filter(self.h, int(stage), t.ctypes.data_as(C.POINTER(C.c_int16)), t.size),
-              "hrfd_duc_set_filter")
-
-    def phase(self, channel: int) -> int:
-        v = C.c_uint32(0)
-        check(self.L.hrfd_duc_get_phase(self.h, int(channel), C.byref(v)), "hrfd_duc_get_phase")
-        return int(v.value)
+        self._set_filter(stage, taps)
 
     def clips(self, capture: int) -> int:
         """output samples (I and Q apart) of the capture that saturated since create / reset; waits for the last call"""
@@ -742,23 +741,15 @@ def tune_from_scan(ddc: "Ddc", stations, first_channel: int = 0):
     return chan_map
 
 
-class Spectrum:
+class Spectrum(_Bank):
     """A bank of windowed integer FFTs (hrfd_spec_*): n_captures wideband int8 IQ captures at decimation x 2.048 MS/s in,
     the power of every bin of a 2^log2_n point transform summed over a call's frames out, and the verdicts of the bands."""
 
+    _prefix = "spec"
+
     def __init__(self, n_captures: int, decimation: int, log2_n: int, device: int = -1):
-        self.L = _lib.load()
         self.W, self.R, self.log2_n, self.N = int(n_captures), int(decimation), int(log2_n), 1 << int(log2_n)
-        h = C.c_void_p()
-        check(self.L.hrfd_spec_create(self.W, self.R, self.log2_n, device, C.byref(h)), "hrfd_spec_create")
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hrfd_spec_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        self._create(self.W, self.R, self.log2_n, device)
 
     def set_window(self, w=None):
         """N int16 values; None restores the default (Hann)"""

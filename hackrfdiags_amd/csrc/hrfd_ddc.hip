@@ -18,15 +18,14 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <mutex>
 #include <vector>
 
 #include "hrfd_ddc_tables.h"
 
 namespace hrfd {
 
-constexpr int kDdcTile = 1024;             // outputs per workgroup
-constexpr int kDdcThreads = 256;
+constexpr int kDdcTile = kBankTile;        // outputs per workgroup
+constexpr int kDdcThreads = kBankThreads;
 constexpr int kDdcMaxTA = 64;
 constexpr int kDdcMaxTB = 256;
 constexpr int kDdcJA = kDdcMaxTA / 2 + 1;  // packed tap dwords per variant
@@ -51,15 +50,6 @@ struct DdcLds
   static __device__ __forceinline__ int dw(int D) { return kH2 == 1 ? D : (D % kH2) * kYS + D / kH2; }
 };
 
-struct DdcChanDev
-{
-  uint32_t capture;
-  uint32_t step;
-  uint32_t theta_ref;
-  uint32_t g;
-  uint64_t n_ref;
-};
-
 struct DdcParams
 {
   const int8_t *cap;           // [W] rows of R * 2M bytes, cap_stride apart
@@ -68,7 +58,7 @@ struct DdcParams
   int8_t *hist_out;            // [W][H]: the H samples in front of the next call
   int8_t *out;                 // [C] rows of 2M bytes, out_stride apart
   uint64_t out_stride;
-  const DdcChanDev *chan;
+  const BankTuning *chan;        // word: the gain shift g
   const uint2 *taps;           // [kDdcJA] stage A (even, odd) pairs, then [kDdcJB] stage B
   const uint32_t *cs;          // [4096] (COS[k], COS[(k - 1024) & 4095]) as packed int16
   uint64_t n0;                 // absolute index of the call's first input sample
@@ -182,7 +172,7 @@ __global__ __launch_bounds__(kDdcThreads) void k_ddc(const DdcParams P)
   const uint32_t c = blockIdx.x / P.n_tiles;
   const int m_t = (int)(blockIdx.x - c * P.n_tiles) * kDdcTile;
   const int cnt = min(kDdcTile, (int)P.M - m_t);
-  const DdcChanDev ch = P.chan[c];
+  const BankTuning ch = P.chan[c];
 
   for (int i = tid; i < 4096; i += kDdcThreads)
   {
@@ -201,7 +191,7 @@ __global__ __launch_bounds__(kDdcThreads) void k_ddc(const DdcParams P)
 
   // 1. mix: pair p holds samples jy0 + 2p, jy0 + 2p + 1
   {
-    const uint32_t theta_call = ch.theta_ref + (uint32_t)(P.n0 - ch.n_ref) * ch.step;
+    const uint32_t theta_call = bank_phase_at(ch, P.n0);
     uint32_t th = theta_call + (uint32_t)(jy0 + 2 * tid) * ch.step;
     const uint32_t dth = (uint32_t)(2 * kDdcThreads) * ch.step;
     for (int p = tid; p < nyd; p += kDdcThreads, th += dth)
@@ -356,7 +346,7 @@ __global__ __launch_bounds__(kDdcThreads) void k_ddc(const DdcParams P)
       bQ[i] = sat16(bQ[i] >> 15);
     }
   }
-  const int g = (int)ch.g;
+  const int g = (int)ch.word;
   const int r = (g < 7) ? (1 << (6 - g)) : 0;
   uint32_t lo = 0, hi = 0;
 #pragma unroll
@@ -400,193 +390,80 @@ template __global__ void k_ddc<8>(const DdcParams);
 // ------------------------------------------------------------------ host side
 struct hrfd_ddc
 {
-  int device = 0;
+  hrfd::BankCore core;
   uint32_t n_captures = 0, n_channels = 0, R = 1, H = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t last_stream = nullptr;       // the stream of the last launch: the next one is ordered behind it
-  hipEvent_t ev_last = nullptr;            // recorded on last_stream when the next launch runs on another stream
-  hipEvent_t ev_upload = nullptr;          // the last upload from the pinned staging buffer has been read
-  hrfd::DdcChanDev *h_stage_chan = nullptr;   // pinned staging of the records and packed taps (uploads in stream order)
-  uint2 *h_stage_taps = nullptr;
+  // pinned staging of the records and packed taps (uploads in stream order)
+  hrfd::PinnedBuf<hrfd::BankTuning> h_stage_chan;
+  hrfd::PinnedBuf<uint2> h_stage_taps;
 
-  std::mutex mu;                           // guards the host records (setters may come from another thread)
-  std::vector<hrfd::DdcChanDev> h_chan;
+  // host records, under core.mu
+  std::vector<hrfd::BankTuning> h_chan;
   std::vector<int16_t> tapsA, tapsB;
   bool dirty = true;
   uint64_t N = 0;                          // absolute input-sample counter
   bool clear_history = true;
 
-  hrfd::DdcChanDev *d_chan = nullptr;
-  uint2 *d_taps = nullptr;
-  uint32_t *d_cs = nullptr;
-  int8_t *d_hist[2] = {nullptr, nullptr};
+  hrfd::DevBuf<hrfd::BankTuning> d_chan;
+  hrfd::DevBuf<uint2> d_taps;
+  hrfd::DevBuf<uint32_t> d_cs;
+  hrfd::DevBuf<int8_t> d_hist[2];
   int cur = 0;
-  int8_t *d_in = nullptr, *d_out = nullptr, *d_rx = nullptr;   // host-path staging and hrfd_ddc_receive's buffer
-  size_t cap_in = 0, cap_out = 0, cap_rx = 0;
-  uint8_t *d_scratch_mag = nullptr;
-  size_t cap_scratch = 0;
+  hrfd::DevBuf<int8_t> d_in, d_out, d_rx;  // host-path staging and hrfd_ddc_receive's buffer
+  hrfd::DevBuf<uint8_t> d_scratch_mag;
 };
-
-static int ddc_taps_ok(const char *who, const int16_t *taps, uint32_t n, uint32_t max_n)
-{
-  if (n > max_n || (n > 0 && taps == nullptr))
-  {
-    return fail(HRFD_EINVAL, "%s: %u taps (at most %u, and a tap array when n > 0)", who, n, max_n);
-  }
-  int64_t sum = 0;
-  for (uint32_t k = 0; k < n; k++)
-  {
-    sum += taps[k] < 0 ? -(int64_t)taps[k] : (int64_t)taps[k];
-  }
-  if (sum > 65535)
-  {
-    return fail(HRFD_EINVAL, "%s: sum |h| = %lld exceeds 65535 (the int32 accumulator could overflow)", who, (long long)sum);
-  }
-  return HRFD_OK;
-}
-
-// (even, odd) packed pairs of the time-reversed taps: x = (g[2j], g[2j+1]), y = (g'[2j], g'[2j+1]) with g' = 0, g
-static void ddc_pack_taps(const std::vector<int16_t> &h, uint2 *out, int J)
-{
-  const int T = (int)h.size();
-  auto g = [&](int i) -> uint32_t { return (i >= 0 && i < T) ? (uint16_t)h[T - 1 - i] : 0u; };
-  for (int j = 0; j < J; j++)
-  {
-    out[j].x = g(2 * j) | (g(2 * j + 1) << 16);
-    out[j].y = g(2 * j - 1) | (g(2 * j) << 16);
-  }
-}
-
-static int ddc_packed_len(int T) { return T > 0 ? T / 2 + 1 : 0; }
 
 extern "C" int hrfd_ddc_create(uint32_t n_captures, uint32_t n_channels, uint32_t decimation, int device, hrfd_ddc **out)
 {
+  using namespace hrfd;
   if (out == nullptr || n_captures == 0 || n_channels == 0)
   {
     return fail(HRFD_EINVAL, "hrfd_ddc_create: need n_captures > 0, n_channels > 0 and a result pointer");
   }
   *out = nullptr;
-  if (decimation != 1 && decimation != 2 && decimation != 4 && decimation != 8)
-  {
-    return fail(HRFD_EINVAL, "hrfd_ddc_create: decimation must be 1, 2, 4 or 8 (got %u)", decimation);
-  }
-  if (hrfd_device_count() <= 0)
-  {
-    return fail(HRFD_ENODEV, "hrfd_ddc_create: no HIP device visible (this library has no CPU path)");
-  }
-  if (device < 0)
-  {
-    HIP_TRY(hipGetDevice(&device));
-  }
-  HIP_TRY(hipSetDevice(device));
-  hrfd_ddc *d = new hrfd_ddc;
-  d->device = device;
+  BANK_TRY(bank_rate_ok("hrfd_ddc_create", "decimation", decimation));
+  hrfd_ddc *d = nullptr;
+  BANK_TRY(bank_new("hrfd_ddc_create", device, &d));
   d->n_captures = n_captures;
   d->n_channels = n_channels;
   d->R = decimation;
   d->H = 255u * decimation + 63u;
-  d->h_chan.assign(n_channels, hrfd::DdcChanDev{0u, 0u, 0u, 0u, 0ull});
+  d->h_chan.assign(n_channels, BankTuning{0u, 0u, 0u, 0u, 0ull});
   switch (decimation)
   {
-  case 2: d->tapsA.assign(hrfd::Q_DDC_A2, hrfd::Q_DDC_A2 + hrfd::N_DDC_A2); break;
-  case 4: d->tapsA.assign(hrfd::Q_DDC_A4, hrfd::Q_DDC_A4 + hrfd::N_DDC_A4); break;
-  case 8: d->tapsA.assign(hrfd::Q_DDC_A8, hrfd::Q_DDC_A8 + hrfd::N_DDC_A8); break;
+  case 2: d->tapsA.assign(Q_DDC_A2, Q_DDC_A2 + N_DDC_A2); break;
+  case 4: d->tapsA.assign(Q_DDC_A4, Q_DDC_A4 + N_DDC_A4); break;
+  case 8: d->tapsA.assign(Q_DDC_A8, Q_DDC_A8 + N_DDC_A8); break;
   default: break;                          // R = 1: stage A in bypass
   }
-  d->tapsB.assign(hrfd::Q_DDC_B, hrfd::Q_DDC_B + hrfd::N_DDC_B);
-  std::vector<uint32_t> cs(4096);
-  for (int k = 0; k < 4096; k++)
-  {
-    cs[k] = (uint16_t)hrfd::Q_DDC_COS[k] | ((uint32_t)(uint16_t)hrfd::Q_DDC_COS[(k - 1024) & 4095] << 16);
-  }
+  d->tapsB.assign(Q_DDC_B, Q_DDC_B + N_DDC_B);
   const size_t hist_bytes = (size_t)n_captures * d->H * 2;
-  bool ok = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_chan, sizeof(hrfd::DdcChanDev) * n_channels) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_taps, sizeof(uint2) * (hrfd::kDdcJA + hrfd::kDdcJB)) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_cs, sizeof(uint32_t) * 4096) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_hist[0], hist_bytes) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_hist[1], hist_bytes) == hipSuccess;
-  ok = ok && hipMemcpy(d->d_cs, cs.data(), sizeof(uint32_t) * 4096, hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&d->ev_last, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&d->ev_upload, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipHostMalloc((void **)&d->h_stage_chan, sizeof(hrfd::DdcChanDev) * n_channels, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipHostMalloc((void **)&d->h_stage_taps, sizeof(uint2) * (hrfd::kDdcJA + hrfd::kDdcJB), hipHostMallocDefault) == hipSuccess;
+  const bool ok = d->d_chan.alloc(n_channels) && d->d_taps.alloc(kDdcJA + kDdcJB) && bank_upload_cos(d->d_cs) &&
+                  d->d_hist[0].alloc(hist_bytes) && d->d_hist[1].alloc(hist_bytes) && d->h_stage_chan.alloc(n_channels) &&
+                  d->h_stage_taps.alloc(kDdcJA + kDdcJB);
   if (!ok)
   {
     (void)hipGetLastError();
-    hrfd_ddc_destroy(d);
+    bank_free(d);
     return fail(HRFD_ENOMEM, "hrfd_ddc_create: device allocation failed");
   }
-  d->last_stream = d->stream;
   *out = d;
   return HRFD_OK;
 }
 
 extern "C" int hrfd_ddc_destroy(hrfd_ddc *d)
 {
-  if (d == nullptr)
+  if (d != nullptr)
   {
-    return HRFD_OK;
+    hrfd::bank_free(d);
   }
-  (void)hipSetDevice(d->device);
-  if (d->stream)
-  {
-    (void)hipStreamSynchronize(d->stream);
-  }
-  if (d->last_stream && d->last_stream != d->stream)
-  {
-    (void)hipStreamSynchronize(d->last_stream);
-  }
-  void *ptrs[] = {d->d_chan, d->d_taps, d->d_cs, d->d_hist[0], d->d_hist[1], d->d_in, d->d_out, d->d_rx, d->d_scratch_mag};
-  for (void *p : ptrs)
-  {
-    if (p) (void)hipFree(p);
-  }
-  if (d->h_stage_chan) (void)hipHostFree(d->h_stage_chan);
-  if (d->h_stage_taps) (void)hipHostFree(d->h_stage_taps);
-  if (d->ev_last) (void)hipEventDestroy(d->ev_last);
-  if (d->ev_upload) (void)hipEventDestroy(d->ev_upload);
-  if (d->stream)
-  {
-    (void)hipStreamDestroy(d->stream);
-  }
-  delete d;
   return HRFD_OK;
 }
 
-extern "C" int hrfd_ddc_reset(hrfd_ddc *d)
-{
-  if (d == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_ddc_reset: NULL handle");
-  }
-  std::lock_guard<std::mutex> g(d->mu);
-  d->N = 0;
-  for (hrfd::DdcChanDev &c : d->h_chan)
-  {
-    c.theta_ref = 0u;
-    c.n_ref = 0ull;
-  }
-  d->clear_history = true;
-  d->dirty = true;
-  return HRFD_OK;
-}
+extern "C" int hrfd_ddc_reset(hrfd_ddc *d) { return hrfd::tuned_reset(d, "hrfd_ddc_reset"); }
 
 extern "C" int hrfd_ddc_set_tuning(hrfd_ddc *d, uint32_t channel, uint32_t capture, uint32_t step)
 {
-  if (d == nullptr || channel >= d->n_channels || capture >= d->n_captures)
-  {
-    return fail(HRFD_EINVAL, "hrfd_ddc_set_tuning: bad handle, channel or capture");
-  }
-  std::lock_guard<std::mutex> g(d->mu);
-  hrfd::DdcChanDev &c = d->h_chan[channel];
-  // phase-continuous at the change point: theta_ref = theta(N) under the old tuning
-  c.theta_ref = c.theta_ref + (uint32_t)(d->N - c.n_ref) * c.step;
-  c.n_ref = d->N;
-  c.step = step;
-  c.capture = capture;
-  d->dirty = true;
-  return HRFD_OK;
+  return hrfd::tuned_set_tuning(d, "hrfd_ddc_set_tuning", channel, capture, step);
 }
 
 extern "C" int hrfd_ddc_set_gain_shift(hrfd_ddc *d, uint32_t channel, uint32_t gshift)
@@ -595,20 +472,7 @@ extern "C" int hrfd_ddc_set_gain_shift(hrfd_ddc *d, uint32_t channel, uint32_t g
   {
     return fail(HRFD_EINVAL, "hrfd_ddc_set_gain_shift: g must be 0..7 (got %u)", gshift);
   }
-  if (d == nullptr || (channel >= d->n_channels && channel != HRFD_ALL_CHANNELS))
-  {
-    return fail(HRFD_EINVAL, "hrfd_ddc_set_gain_shift: bad handle or channel");
-  }
-  std::lock_guard<std::mutex> g(d->mu);
-  for (uint32_t c = 0; c < d->n_channels; c++)
-  {
-    if (channel == HRFD_ALL_CHANNELS || c == channel)
-    {
-      d->h_chan[c].g = gshift;
-    }
-  }
-  d->dirty = true;
-  return HRFD_OK;
+  return hrfd::tuned_set_word(d, "hrfd_ddc_set_gain_shift", channel, gshift);
 }
 
 extern "C" int hrfd_ddc_set_filter(hrfd_ddc *d, int stage, const int16_t *taps, uint32_t n)
@@ -617,16 +481,13 @@ extern "C" int hrfd_ddc_set_filter(hrfd_ddc *d, int stage, const int16_t *taps, 
   {
     return fail(HRFD_EINVAL, "hrfd_ddc_set_filter: stage must be 0 (A) or 1 (B) (got %d)", stage);
   }
-  const int rc = ddc_taps_ok("hrfd_ddc_set_filter", taps, n, stage == 0 ? hrfd::kDdcMaxTA : hrfd::kDdcMaxTB);
-  if (rc != HRFD_OK)
-  {
-    return rc;
-  }
+  BANK_TRY(hrfd::bank_tap_count_ok("hrfd_ddc_set_filter", taps, n, stage == 0 ? hrfd::kDdcMaxTA : hrfd::kDdcMaxTB));
+  BANK_TRY(hrfd::bank_tap_sums_ok("hrfd_ddc_set_filter", taps, n, 1u));
   if (d == nullptr)
   {
     return fail(HRFD_EINVAL, "hrfd_ddc_set_filter: NULL handle");
   }
-  std::lock_guard<std::mutex> g(d->mu);
+  std::lock_guard<std::mutex> g(d->core.mu);
   (stage == 0 ? d->tapsA : d->tapsB).assign(taps, taps + n);
   d->dirty = true;
   return HRFD_OK;
@@ -634,14 +495,7 @@ extern "C" int hrfd_ddc_set_filter(hrfd_ddc *d, int stage, const int16_t *taps, 
 
 extern "C" int hrfd_ddc_get_phase(hrfd_ddc *d, uint32_t channel, uint32_t *theta)
 {
-  if (d == nullptr || channel >= d->n_channels || theta == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_ddc_get_phase: bad handle, channel or NULL result");
-  }
-  std::lock_guard<std::mutex> g(d->mu);
-  const hrfd::DdcChanDev &c = d->h_chan[channel];
-  *theta = c.theta_ref + (uint32_t)(d->N - c.n_ref) * c.step;
-  return HRFD_OK;
+  return hrfd::tuned_get_phase(d, "hrfd_ddc_get_phase", channel, theta);
 }
 
 // one launch over every channel on `s`: out_bytes per channel from R * out_bytes per capture
@@ -649,28 +503,22 @@ static int ddc_launch(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_st
                       uint64_t out_stride, hipStream_t s)
 {
   using namespace hrfd;
-  // The history ping-pong and the records are the handle's: a launch on another stream than the last one waits for it
-  // on the device (without it, this launch would read the history the last one is still writing).
-  if (s != d->last_stream)
-  {
-    HIP_TRY(hipEventRecord(d->ev_last, d->last_stream));
-    HIP_TRY(hipStreamWaitEvent(s, d->ev_last, 0));
-  }
+  // without this wait, the launch would read the history the last one is still writing
+  BANK_TRY(d->core.order_behind_last(s));
   DdcParams P;
   {
-    std::lock_guard<std::mutex> g(d->mu);
+    std::lock_guard<std::mutex> g(d->core.mu);
     if (d->dirty || d->clear_history)
     {
-      // records, taps and a cleared history go to the device on `s`, ahead of this launch; the pinned staging buffer
-      // is rewritten only once the device has read the previous upload out of it
-      HIP_TRY(hipEventSynchronize(d->ev_upload));
-      memcpy(d->h_stage_chan, d->h_chan.data(), sizeof(DdcChanDev) * d->n_channels);
+      // records, taps and a cleared history go to the device on `s`, ahead of this launch
+      BANK_TRY(d->core.staging_wait());
+      memcpy(d->h_stage_chan, d->h_chan.data(), sizeof(BankTuning) * d->n_channels);
       memset(d->h_stage_taps, 0, sizeof(uint2) * (kDdcJA + kDdcJB));
-      ddc_pack_taps(d->tapsA, d->h_stage_taps, ddc_packed_len((int)d->tapsA.size()));
-      ddc_pack_taps(d->tapsB, d->h_stage_taps + kDdcJA, ddc_packed_len((int)d->tapsB.size()));
-      HIP_TRY(hipMemcpyAsync(d->d_chan, d->h_stage_chan, sizeof(DdcChanDev) * d->n_channels, hipMemcpyHostToDevice, s));
+      bank_pack_taps(d->tapsA.data(), (int)d->tapsA.size(), d->h_stage_taps.p, bank_packed_len((int)d->tapsA.size()));
+      bank_pack_taps(d->tapsB.data(), (int)d->tapsB.size(), d->h_stage_taps + kDdcJA, bank_packed_len((int)d->tapsB.size()));
+      HIP_TRY(hipMemcpyAsync(d->d_chan, d->h_stage_chan, sizeof(BankTuning) * d->n_channels, hipMemcpyHostToDevice, s));
       HIP_TRY(hipMemcpyAsync(d->d_taps, d->h_stage_taps, sizeof(uint2) * (kDdcJA + kDdcJB), hipMemcpyHostToDevice, s));
-      HIP_TRY(hipEventRecord(d->ev_upload, s));
+      BANK_TRY(d->core.staging_sent(s));
       if (d->clear_history)
       {
         HIP_TRY(hipMemsetAsync(d->d_hist[d->cur], 0, (size_t)d->n_captures * d->H * 2, s));
@@ -697,8 +545,8 @@ static int ddc_launch(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_st
   P.n_channels = d->n_channels;
   P.n_captures = d->n_captures;
   P.H = d->H;
-  P.JA = ddc_packed_len(P.TA);
-  P.JB = ddc_packed_len(P.TB);
+  P.JA = bank_packed_len(P.TA);
+  P.JB = bank_packed_len(P.TB);
   const dim3 grid(P.n_tiles * d->n_channels + d->n_captures);
   switch (d->R)
   {
@@ -711,12 +559,12 @@ static int ddc_launch(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_st
   if (e != hipSuccess)
   {
     // the counter and the history advance only with a launch that was accepted
-    std::lock_guard<std::mutex> g(d->mu);
+    std::lock_guard<std::mutex> g(d->core.mu);
     d->N = P.n0;
     return fail(HRFD_ENODEV, "k_ddc launch failed: %s", hipGetErrorString(e));
   }
   d->cur ^= 1;
-  d->last_stream = s;
+  d->core.launched_on(s);
   return HRFD_OK;
 }
 
@@ -727,56 +575,29 @@ static int ddc_check_call(hrfd_ddc *d, const void *captures, uint64_t capture_st
   {
     return fail(HRFD_EINVAL, "%s: NULL argument", who);
   }
-  if (out_bytes < 2 || (out_bytes & 1u) != 0 || out_bytes > (1u << 25))
-  {
-    return fail(HRFD_EINVAL, "%s: out_bytes must be even, >= 2 and <= 2^25 (got %u)", who, out_bytes);
-  }
-  // one launch: gridDim.x * blockDim.x work-items must fit in 32 bits
-  if ((uint64_t)d->n_channels * ((out_bytes / 2u + hrfd::kDdcTile - 1) / hrfd::kDdcTile) + d->n_captures >
-      0xffffffffull / hrfd::kDdcThreads)
-  {
-    return fail(HRFD_EINVAL, "%s: %u channels x %u bytes need more workgroups than one launch takes", who, d->n_channels,
-                out_bytes);
-  }
-  if (capture_stride < (uint64_t)d->R * out_bytes || out_stride < out_bytes || (capture_stride & 1u) != 0 ||
-      ((uintptr_t)captures & 1u) != 0)
-  {
-    return fail(HRFD_EINVAL, "%s: strides shorter than a row, or an odd capture stride / address", who);
-  }
-  return HRFD_OK;
+  return hrfd::bank_check_call(who, "out_bytes", out_bytes, captures, capture_stride, d->R, out_stride, 1u, d->n_channels,
+                               d->n_captures);
 }
 
 extern "C" int hrfd_ddc_process_device(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_stride, uint32_t out_bytes,
                                        int8_t *d_out, uint64_t out_stride, void *stream)
 {
-  int rc = ddc_check_call(d, d_captures, capture_stride, out_bytes, d_out, out_stride, "hrfd_ddc_process_device");
-  if (rc != HRFD_OK)
-  {
-    return rc;
-  }
-  HIP_TRY(hipSetDevice(d->device));
-  return ddc_launch(d, d_captures, capture_stride, out_bytes, d_out, out_stride,
-                    stream ? (hipStream_t)stream : d->stream);
+  BANK_TRY(ddc_check_call(d, d_captures, capture_stride, out_bytes, d_out, out_stride, "hrfd_ddc_process_device"));
+  HIP_TRY(hipSetDevice(d->core.device));
+  return ddc_launch(d, d_captures, capture_stride, out_bytes, d_out, out_stride, d->core.stream_or_own(stream));
 }
 
 extern "C" int hrfd_ddc_process(hrfd_ddc *d, const int8_t *captures, uint32_t out_bytes, int8_t *out)
 {
-  int rc = ddc_check_call(d, captures, d ? (uint64_t)d->R * out_bytes : 0, out_bytes, out, out_bytes, "hrfd_ddc_process");
-  if (rc != HRFD_OK)
-  {
-    return rc;
-  }
-  HIP_TRY(hipSetDevice(d->device));
-  hipStream_t s = d->stream;
-  HIP_TRY(hipStreamSynchronize(s));
+  BANK_TRY(ddc_check_call(d, captures, d ? (uint64_t)d->R * out_bytes : 0, out_bytes, out, out_bytes, "hrfd_ddc_process"));
+  HIP_TRY(hipSetDevice(d->core.device));
+  hipStream_t s = d->core.stream;
+  BANK_TRY(d->core.drain());
   const size_t in_bytes = (size_t)d->n_captures * d->R * out_bytes, out_total = (size_t)d->n_channels * out_bytes;
-  if ((rc = grow((void **)&d->d_in, &d->cap_in, in_bytes)) != HRFD_OK) return rc;
-  if ((rc = grow((void **)&d->d_out, &d->cap_out, out_total)) != HRFD_OK) return rc;
+  BANK_TRY(d->d_in.grow(in_bytes));
+  BANK_TRY(d->d_out.grow(out_total));
   HIP_TRY(hipMemcpyAsync(d->d_in, captures, in_bytes, hipMemcpyHostToDevice, s));
-  if ((rc = ddc_launch(d, d->d_in, (uint64_t)d->R * out_bytes, out_bytes, d->d_out, out_bytes, s)) != HRFD_OK)
-  {
-    return rc;
-  }
+  BANK_TRY(ddc_launch(d, d->d_in, (uint64_t)d->R * out_bytes, out_bytes, d->d_out, out_bytes, s));
   HIP_TRY(hipMemcpyAsync(out, d->d_out, out_total, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return HRFD_OK;
@@ -801,40 +622,30 @@ extern "C" int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captur
                 "bytes per channel (got %u x %u)", HRFD_BLOCK_BYTES, block_bytes, n_blocks);
   }
   const uint32_t out_bytes = block_bytes * n_blocks;
-  int rc = ddc_check_call(d, d_captures, capture_stride, out_bytes, d_pcm, out_bytes, "hrfd_ddc_receive");
-  if (rc != HRFD_OK)
+  BANK_TRY(ddc_check_call(d, d_captures, capture_stride, out_bytes, d_pcm, out_bytes, "hrfd_ddc_receive"));
+  if (rx->device != d->core.device)
   {
-    return rc;
+    return fail(HRFD_EINVAL, "hrfd_ddc_receive: the rx handle lives on device %d, the DDC on %d", rx->device, d->core.device);
   }
-  if (rx->device != d->device)
-  {
-    return fail(HRFD_EINVAL, "hrfd_ddc_receive: the rx handle lives on device %d, the DDC on %d", rx->device, d->device);
-  }
-  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipSetDevice(d->core.device));
   hipStream_t s = rx->stream;
   const uint32_t C = d->n_channels;
   const size_t units = (size_t)C * n_blocks;
   HIP_TRY(hipStreamSynchronize(s));
-  if ((rc = grow((void **)&d->d_rx, &d->cap_rx, (size_t)C * out_bytes)) != HRFD_OK) return rc;
+  BANK_TRY(d->d_rx.grow((size_t)C * out_bytes));
   if (d_magnitude == nullptr || d_signal_allowed == nullptr)
   {
     // the rx launches always write both: scratch rows for the ones the caller does not want
-    if ((rc = grow((void **)&d->d_scratch_mag, &d->cap_scratch, units * 5)) != HRFD_OK) return rc;
+    BANK_TRY(d->d_scratch_mag.grow(units * 5));
   }
-  uint32_t *mag = d_magnitude ? d_magnitude : (uint32_t *)d->d_scratch_mag;
-  uint8_t *allowed = d_signal_allowed ? d_signal_allowed : (uint8_t *)d->d_scratch_mag + units * 4;
-  if ((rc = ddc_launch(d, d_captures, capture_stride, out_bytes, d->d_rx, out_bytes, s)) != HRFD_OK)
-  {
-    return rc;
-  }
+  uint32_t *mag = d_magnitude ? d_magnitude : (uint32_t *)d->d_scratch_mag.p;
+  uint8_t *allowed = d_signal_allowed ? d_signal_allowed : d->d_scratch_mag + units * 4;
+  BANK_TRY(ddc_launch(d, d_captures, capture_stride, out_bytes, d->d_rx, out_bytes, s));
   // mode NONE / squelched units produce no PCM: zeros, as hrfd_rx_process_block hands back
   HIP_TRY(hipMemsetAsync(d_pcm, 0, units * ((block_bytes + 511u) / 512u) * sizeof(int16_t), s));
   uint32_t replayed = 0;
-  if ((rc = rx_run_batch(rx, d->d_rx, block_bytes, n_blocks, gain_db, d_pcm, d_n_pcm, mag, allowed, nullptr, s,
-                         &replayed)) != HRFD_OK)
-  {
-    return rc;
-  }
+  BANK_TRY(rx_run_batch(rx, d->d_rx, block_bytes, n_blocks, gain_db, d_pcm, d_n_pcm, mag, allowed, nullptr, s,
+                         &replayed));
   HIP_TRY(hipStreamSynchronize(s));
   if (n_replayed != nullptr)
   {

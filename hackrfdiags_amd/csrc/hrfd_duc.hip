@@ -20,15 +20,14 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <mutex>
 #include <vector>
 
 #include "hrfd_duc_tables.h"
 
 namespace hrfd {
 
-constexpr int kDucTile = 1024;             // channel samples per workgroup
-constexpr int kDucThreads = 256;
+constexpr int kDucTile = kBankTile;        // channel samples per workgroup
+constexpr int kDucThreads = kBankThreads;
 constexpr int kDucMaxTA = 64;
 constexpr int kDucMaxTB = 256;
 constexpr int kDucH = 318;                 // history: stage B's 255 samples behind stage A's 63 (R = 1)
@@ -41,15 +40,6 @@ constexpr int kDucUDw = (kDucH + kDucTile + 16) / 2 + 8;
 // v rails: kDucTile + LA (<= 63) samples rounded up to quads, plus the last window's overrun
 constexpr int kDucVDw = (kDucTile + 64 + 8) / 2 + 8;
 
-struct DucChanDev
-{
-  uint32_t capture;
-  uint32_t step;
-  uint32_t theta_ref;
-  uint32_t amp;
-  uint64_t n_ref;
-};
-
 struct DucParams
 {
   const int8_t *in;            // [C] rows of 2M bytes, in_stride apart
@@ -58,7 +48,7 @@ struct DucParams
   int8_t *hist_out;            // [C][kDucH]: the samples in front of the next call
   int8_t *cap;                 // [W] rows of 2 R M bytes, cap_stride apart
   uint64_t cap_stride;
-  const DucChanDev *chan;
+  const BankTuning *chan;        // word: the amplitude A
   const uint32_t *list_off;    // [W + 1]: the channels of capture w are list[list_off[w] .. list_off[w + 1])
   const uint32_t *list;        // [C]
   const uint32_t *shift;       // [W] output shifts
@@ -170,8 +160,8 @@ __global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
   for (uint32_t ci = P.list_off[w]; ci < c_end; ci++)
   {
     const uint32_t c = P.list[ci];
-    const DucChanDev ch = P.chan[c];
-    if (ch.amp == 0u)
+    const BankTuning ch = P.chan[c];
+    if (ch.word == 0u)
     {
       continue;                                         // muted: every y is 0 (uniform over the workgroup)
     }
@@ -185,7 +175,7 @@ __global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
     __syncthreads();
 
     // 2. stage B and the amplitude: v index 4q + i
-    const int amp = (int)ch.amp;
+    const int amp = (int)ch.word;
     for (int q = tid; q < nq; q += kDucThreads)
     {
       int bI[4], bQ[4];
@@ -230,7 +220,7 @@ __global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
     __syncthreads();
 
     // 3. stage A, mixer, sum: positions m, m + 1 of pair h (v indices m + LA, m + 1 + LA), outputs (m_t + m) R + i
-    const uint32_t theta_call = ch.theta_ref + (uint32_t)(P.n0 - ch.n_ref) * ch.step;
+    const uint32_t theta_call = bank_phase_at(ch, P.n0);
 #pragma unroll
     for (int h = 0; h < 2; h++)
     {
@@ -366,91 +356,34 @@ template __global__ void k_duc<8>(const DucParams);
 // ------------------------------------------------------------------ host side
 struct hrfd_duc
 {
-  int device = 0;
+  hrfd::BankCore core;
   uint32_t n_captures = 0, n_channels = 0, R = 1;
-  hipStream_t stream = nullptr;
-  hipStream_t last_stream = nullptr;       // the stream of the last launch: the next one is ordered behind it
-  hipEvent_t ev_last = nullptr;            // recorded on last_stream when the next launch runs on another stream
-  hipEvent_t ev_upload = nullptr;          // the last upload from the pinned staging buffer has been read
   // pinned staging of the records, the channel lists, the shifts and the packed taps (uploads in stream order)
-  hrfd::DucChanDev *h_stage_chan = nullptr;
-  uint32_t *h_stage_u32 = nullptr;         // [W + 1] list offsets, [C] list, [W] shifts
-  uint2 *h_stage_taps = nullptr;
+  hrfd::PinnedBuf<hrfd::BankTuning> h_stage_chan;
+  hrfd::PinnedBuf<uint32_t> h_stage_u32;   // [W + 1] list offsets, [C] list, [W] shifts
+  hrfd::PinnedBuf<uint2> h_stage_taps;
 
-  std::mutex mu;                           // guards the host records (setters may come from another thread)
-  std::vector<hrfd::DucChanDev> h_chan;
+  // host records, under core.mu
+  std::vector<hrfd::BankTuning> h_chan;
   std::vector<uint32_t> h_shift;
   std::vector<int16_t> tapsA, tapsB;
   bool dirty = true;
   uint64_t N = 0;                          // absolute wideband output-sample counter
   bool clear_history = true;               // also clears the clip counters
 
-  hrfd::DucChanDev *d_chan = nullptr;
-  uint32_t *d_u32 = nullptr;
-  uint2 *d_taps = nullptr;
-  uint32_t *d_cs = nullptr;
-  unsigned long long *d_clips = nullptr;
-  int8_t *d_hist[2] = {nullptr, nullptr};
+  hrfd::DevBuf<hrfd::BankTuning> d_chan;
+  hrfd::DevBuf<uint32_t> d_u32;
+  hrfd::DevBuf<uint2> d_taps;
+  hrfd::DevBuf<uint32_t> d_cs;
+  hrfd::DevBuf<unsigned long long> d_clips;
+  hrfd::DevBuf<int8_t> d_hist[2];
   int cur = 0;
-  int8_t *d_in = nullptr, *d_out = nullptr, *d_tx = nullptr;   // host-path staging and hrfd_duc_transmit's buffer
-  size_t cap_in = 0, cap_out = 0, cap_tx = 0;
+  hrfd::DevBuf<int8_t> d_in, d_out, d_tx;  // host-path staging and hrfd_duc_transmit's buffer
 };
-
-static int duc_la(int TA, int R) { return TA > 0 ? (TA - 1) / R : 0; }
-
-static int duc_taps_ok(const char *who, int stage, const int16_t *taps, uint32_t n, uint32_t R)
-{
-  if (stage == 1)
-  {
-    return ddc_taps_ok(who, taps, n, hrfd::kDucMaxTB);
-  }
-  if (n > (uint32_t)hrfd::kDucMaxTA || (n > 0 && taps == nullptr))
-  {
-    return fail(HRFD_EINVAL, "%s: %u taps (at most %d, and a tap array when n > 0)", who, n, hrfd::kDucMaxTA);
-  }
-  for (uint32_t p = 0; p < R; p++)
-  {
-    int64_t sum = 0;
-    for (uint32_t k = p; k < n; k += R)
-    {
-      sum += taps[k] < 0 ? -(int64_t)taps[k] : (int64_t)taps[k];
-    }
-    if (sum > 65535)
-    {
-      return fail(HRFD_EINVAL, "%s: branch %u has sum |h| = %lld > 65535 (the int32 accumulator could overflow)", who, p,
-                  (long long)sum);
-    }
-  }
-  return HRFD_OK;
-}
-
-static void duc_free(hrfd_duc *d)
-{
-  (void)hipSetDevice(d->device);
-  if (d->stream)
-  {
-    (void)hipStreamSynchronize(d->stream);
-  }
-  if (d->last_stream && d->last_stream != d->stream)
-  {
-    (void)hipStreamSynchronize(d->last_stream);
-  }
-  void *ptrs[] = {d->d_chan, d->d_u32, d->d_taps, d->d_cs, d->d_clips, d->d_hist[0], d->d_hist[1], d->d_in, d->d_out, d->d_tx};
-  for (void *p : ptrs)
-  {
-    if (p) (void)hipFree(p);
-  }
-  if (d->h_stage_chan) (void)hipHostFree(d->h_stage_chan);
-  if (d->h_stage_u32) (void)hipHostFree(d->h_stage_u32);
-  if (d->h_stage_taps) (void)hipHostFree(d->h_stage_taps);
-  if (d->ev_last) (void)hipEventDestroy(d->ev_last);
-  if (d->ev_upload) (void)hipEventDestroy(d->ev_upload);
-  if (d->stream) (void)hipStreamDestroy(d->stream);
-  delete d;
-}
 
 extern "C" int hrfd_duc_create(uint32_t n_captures, uint32_t n_channels, uint32_t interpolation, int device, hrfd_duc **out)
 {
+  using namespace hrfd;
   if (out != nullptr)
   {
     *out = nullptr;
@@ -459,72 +392,43 @@ extern "C" int hrfd_duc_create(uint32_t n_captures, uint32_t n_channels, uint32_
   {
     return fail(HRFD_EINVAL, "hrfd_duc_create: need n_captures > 0, n_channels > 0 and a result pointer");
   }
-  if (n_channels > hrfd::kDucMaxChannels)
+  if (n_channels > kDucMaxChannels)
   {
-    return fail(HRFD_EINVAL, "hrfd_duc_create: at most %u channels (the int32 sums), got %u", hrfd::kDucMaxChannels,
-                n_channels);
+    return fail(HRFD_EINVAL, "hrfd_duc_create: at most %u channels (the int32 sums), got %u", kDucMaxChannels, n_channels);
   }
-  if (interpolation != 1 && interpolation != 2 && interpolation != 4 && interpolation != 8)
-  {
-    return fail(HRFD_EINVAL, "hrfd_duc_create: interpolation must be 1, 2, 4 or 8 (got %u)", interpolation);
-  }
+  BANK_TRY(bank_rate_ok("hrfd_duc_create", "interpolation", interpolation));
   if (n_captures > 65536)
   {
     return fail(HRFD_EINVAL, "hrfd_duc_create: at most 65536 captures (got %u)", n_captures);
   }
-  if (hrfd_device_count() <= 0)
-  {
-    return fail(HRFD_ENODEV, "hrfd_duc_create: no HIP device visible (this library has no CPU path)");
-  }
-  if (device < 0)
-  {
-    HIP_TRY(hipGetDevice(&device));
-  }
-  HIP_TRY(hipSetDevice(device));
-  hrfd_duc *d = new hrfd_duc;
-  d->device = device;
+  hrfd_duc *d = nullptr;
+  BANK_TRY(bank_new("hrfd_duc_create", device, &d));
   d->n_captures = n_captures;
   d->n_channels = n_channels;
   d->R = interpolation;
-  d->h_chan.assign(n_channels, hrfd::DucChanDev{0u, 0u, 0u, 32768u, 0ull});
+  d->h_chan.assign(n_channels, BankTuning{0u, 0u, 0u, 32768u, 0ull});
   d->h_shift.assign(n_captures, 8u);
   switch (interpolation)
   {
-  case 2: d->tapsA.assign(hrfd::Q_DUC_A2, hrfd::Q_DUC_A2 + hrfd::N_DUC_A2); break;
-  case 4: d->tapsA.assign(hrfd::Q_DUC_A4, hrfd::Q_DUC_A4 + hrfd::N_DUC_A4); break;
-  case 8: d->tapsA.assign(hrfd::Q_DUC_A8, hrfd::Q_DUC_A8 + hrfd::N_DUC_A8); break;
+  case 2: d->tapsA.assign(Q_DUC_A2, Q_DUC_A2 + N_DUC_A2); break;
+  case 4: d->tapsA.assign(Q_DUC_A4, Q_DUC_A4 + N_DUC_A4); break;
+  case 8: d->tapsA.assign(Q_DUC_A8, Q_DUC_A8 + N_DUC_A8); break;
   default: break;                          // R = 1: stage A holds
   }
-  d->tapsB.assign(hrfd::Q_DDC_B, hrfd::Q_DDC_B + hrfd::N_DDC_B);
-  std::vector<uint32_t> cs(4096);
-  for (int k = 0; k < 4096; k++)
-  {
-    cs[k] = (uint16_t)hrfd::Q_DDC_COS[k] | ((uint32_t)(uint16_t)hrfd::Q_DDC_COS[(k - 1024) & 4095] << 16);
-  }
-  const size_t hist_bytes = (size_t)n_channels * hrfd::kDucH * 2;
+  d->tapsB.assign(Q_DDC_B, Q_DDC_B + N_DDC_B);
+  const size_t hist_bytes = (size_t)n_channels * kDucH * 2;
   const size_t n_u32 = 2 * (size_t)n_captures + 1 + n_channels;
-  const size_t n_taps = hrfd::kDucJA + hrfd::kDucJB;
-  bool ok = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_chan, sizeof(hrfd::DucChanDev) * n_channels) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_u32, sizeof(uint32_t) * n_u32) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_taps, sizeof(uint2) * n_taps) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_cs, sizeof(uint32_t) * 4096) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_clips, sizeof(unsigned long long) * n_captures) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_hist[0], hist_bytes) == hipSuccess;
-  ok = ok && hipMalloc((void **)&d->d_hist[1], hist_bytes) == hipSuccess;
-  ok = ok && hipMemcpy(d->d_cs, cs.data(), sizeof(uint32_t) * 4096, hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&d->ev_last, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&d->ev_upload, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipHostMalloc((void **)&d->h_stage_chan, sizeof(hrfd::DucChanDev) * n_channels, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipHostMalloc((void **)&d->h_stage_u32, sizeof(uint32_t) * n_u32, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipHostMalloc((void **)&d->h_stage_taps, sizeof(uint2) * n_taps, hipHostMallocDefault) == hipSuccess;
+  const size_t n_taps = kDucJA + kDucJB;
+  const bool ok = d->d_chan.alloc(n_channels) && d->d_u32.alloc(n_u32) && d->d_taps.alloc(n_taps) &&
+                  bank_upload_cos(d->d_cs) && d->d_clips.alloc(n_captures) && d->d_hist[0].alloc(hist_bytes) &&
+                  d->d_hist[1].alloc(hist_bytes) && d->h_stage_chan.alloc(n_channels) && d->h_stage_u32.alloc(n_u32) &&
+                  d->h_stage_taps.alloc(n_taps);
   if (!ok)
   {
     (void)hipGetLastError();
-    duc_free(d);
+    bank_free(d);
     return fail(HRFD_ENOMEM, "hrfd_duc_create: device allocation failed");
   }
-  d->last_stream = d->stream;
   *out = d;
   return HRFD_OK;
 }
@@ -533,44 +437,16 @@ extern "C" int hrfd_duc_destroy(hrfd_duc *d)
 {
   if (d != nullptr)
   {
-    duc_free(d);
+    hrfd::bank_free(d);
   }
   return HRFD_OK;
 }
 
-extern "C" int hrfd_duc_reset(hrfd_duc *d)
-{
-  if (d == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_duc_reset: NULL handle");
-  }
-  std::lock_guard<std::mutex> g(d->mu);
-  d->N = 0;
-  for (hrfd::DucChanDev &c : d->h_chan)
-  {
-    c.theta_ref = 0u;
-    c.n_ref = 0ull;
-  }
-  d->clear_history = true;
-  d->dirty = true;
-  return HRFD_OK;
-}
+extern "C" int hrfd_duc_reset(hrfd_duc *d) { return hrfd::tuned_reset(d, "hrfd_duc_reset"); }
 
 extern "C" int hrfd_duc_set_tuning(hrfd_duc *d, uint32_t channel, uint32_t capture, uint32_t step)
 {
-  if (d == nullptr || channel >= d->n_channels || capture >= d->n_captures)
-  {
-    return fail(HRFD_EINVAL, "hrfd_duc_set_tuning: bad handle, channel or capture");
-  }
-  std::lock_guard<std::mutex> g(d->mu);
-  hrfd::DucChanDev &c = d->h_chan[channel];
-  // phase-continuous at the change point: theta_ref = theta(N) under the old tuning
-  c.theta_ref = c.theta_ref + (uint32_t)(d->N - c.n_ref) * c.step;
-  c.n_ref = d->N;
-  c.step = step;
-  c.capture = capture;
-  d->dirty = true;
-  return HRFD_OK;
+  return hrfd::tuned_set_tuning(d, "hrfd_duc_set_tuning", channel, capture, step);
 }
 
 extern "C" int hrfd_duc_set_amplitude(hrfd_duc *d, uint32_t channel, uint32_t amplitude)
@@ -579,20 +455,7 @@ extern "C" int hrfd_duc_set_amplitude(hrfd_duc *d, uint32_t channel, uint32_t am
   {
     return fail(HRFD_EINVAL, "hrfd_duc_set_amplitude: A must be 0..32768 (got %u)", amplitude);
   }
-  if (d == nullptr || (channel >= d->n_channels && channel != HRFD_ALL_CHANNELS))
-  {
-    return fail(HRFD_EINVAL, "hrfd_duc_set_amplitude: bad handle or channel");
-  }
-  std::lock_guard<std::mutex> g(d->mu);
-  for (uint32_t c = 0; c < d->n_channels; c++)
-  {
-    if (channel == HRFD_ALL_CHANNELS || c == channel)
-    {
-      d->h_chan[c].amp = amplitude;
-    }
-  }
-  d->dirty = true;
-  return HRFD_OK;
+  return hrfd::tuned_set_word(d, "hrfd_duc_set_amplitude", channel, amplitude);
 }
 
 extern "C" int hrfd_duc_set_output_shift(hrfd_duc *d, uint32_t capture, uint32_t s)
@@ -605,7 +468,7 @@ extern "C" int hrfd_duc_set_output_shift(hrfd_duc *d, uint32_t capture, uint32_t
   {
     return fail(HRFD_EINVAL, "hrfd_duc_set_output_shift: bad handle or capture");
   }
-  std::lock_guard<std::mutex> g(d->mu);
+  std::lock_guard<std::mutex> g(d->core.mu);
   for (uint32_t w = 0; w < d->n_captures; w++)
   {
     if (capture == HRFD_ALL_CHANNELS || w == capture)
@@ -624,20 +487,20 @@ extern "C" int hrfd_duc_set_filter(hrfd_duc *d, int stage, const int16_t *taps, 
     return fail(HRFD_EINVAL, "hrfd_duc_set_filter: stage must be 0 (A) or 1 (B) (got %d)", stage);
   }
   // the tap count, and stage B's sum, need no handle; stage A's bound is per polyphase branch of the handle's R
-  int rc = duc_taps_ok("hrfd_duc_set_filter", stage, taps, n, 1u);
-  if (rc != HRFD_OK && (stage == 1 || n > (uint32_t)hrfd::kDucMaxTA || (n > 0 && taps == nullptr)))
+  BANK_TRY(hrfd::bank_tap_count_ok("hrfd_duc_set_filter", taps, n, stage == 0 ? hrfd::kDucMaxTA : hrfd::kDucMaxTB));
+  if (stage == 1)
   {
-    return rc;
+    BANK_TRY(hrfd::bank_tap_sums_ok("hrfd_duc_set_filter", taps, n, 1u));
   }
   if (d == nullptr)
   {
     return fail(HRFD_EINVAL, "hrfd_duc_set_filter: NULL handle");
   }
-  if ((rc = duc_taps_ok("hrfd_duc_set_filter", stage, taps, n, d->R)) != HRFD_OK)
+  if (stage == 0)
   {
-    return rc;
+    BANK_TRY(hrfd::bank_tap_sums_ok("hrfd_duc_set_filter", taps, n, d->R));
   }
-  std::lock_guard<std::mutex> g(d->mu);
+  std::lock_guard<std::mutex> g(d->core.mu);
   (stage == 0 ? d->tapsA : d->tapsB).assign(taps, taps + n);
   d->dirty = true;
   return HRFD_OK;
@@ -645,14 +508,7 @@ extern "C" int hrfd_duc_set_filter(hrfd_duc *d, int stage, const int16_t *taps, 
 
 extern "C" int hrfd_duc_get_phase(hrfd_duc *d, uint32_t channel, uint32_t *theta)
 {
-  if (d == nullptr || channel >= d->n_channels || theta == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_duc_get_phase: bad handle, channel or NULL result");
-  }
-  std::lock_guard<std::mutex> g(d->mu);
-  const hrfd::DucChanDev &c = d->h_chan[channel];
-  *theta = c.theta_ref + (uint32_t)(d->N - c.n_ref) * c.step;
-  return HRFD_OK;
+  return hrfd::tuned_get_phase(d, "hrfd_duc_get_phase", channel, theta);
 }
 
 extern "C" int hrfd_duc_get_clips(hrfd_duc *d, uint32_t capture, uint64_t *n)
@@ -661,36 +517,20 @@ extern "C" int hrfd_duc_get_clips(hrfd_duc *d, uint32_t capture, uint64_t *n)
   {
     return fail(HRFD_EINVAL, "hrfd_duc_get_clips: bad handle, capture or NULL result");
   }
-  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipSetDevice(d->core.device));
   {
-    std::lock_guard<std::mutex> g(d->mu);
+    std::lock_guard<std::mutex> g(d->core.mu);
     if (d->clear_history)
     {
       *n = 0;                              // no launch since create or reset
       return HRFD_OK;
     }
   }
-  HIP_TRY(hipStreamSynchronize(d->last_stream));
+  HIP_TRY(hipStreamSynchronize(d->core.last_stream));
   unsigned long long v = 0;
   HIP_TRY(hipMemcpy(&v, d->d_clips + capture, sizeof(v), hipMemcpyDeviceToHost));
   *n = (uint64_t)v;
   return HRFD_OK;
-}
-
-// stage A's taps as R branches of LA + 1 taps each, packed like ddc_pack_taps: branch p, tap j = hA[p + j R]
-static void duc_pack_taps_a(const std::vector<int16_t> &h, int R, uint2 *out, int JA)
-{
-  const int T = (int)h.size();
-  const int LA = duc_la(T, R);
-  for (int p = 0; p < R; p++)
-  {
-    std::vector<int16_t> hp(LA + 1, 0);
-    for (int j = 0; j <= LA; j++)
-    {
-      hp[j] = (p + j * R < T) ? h[p + j * R] : (int16_t)0;
-    }
-    ddc_pack_taps(hp, out + p * JA, JA);
-  }
 }
 
 // one launch over every capture on `s`: R * in_bytes per capture from in_bytes per channel
@@ -698,55 +538,35 @@ static int duc_launch(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_st
                       uint64_t capture_stride, hipStream_t s)
 {
   using namespace hrfd;
-  // The history ping-pong, the records and the clip counters are the handle's: a launch on another stream than the last
-  // one waits for it on the device.
-  if (s != d->last_stream)
-  {
-    HIP_TRY(hipEventRecord(d->ev_last, d->last_stream));
-    HIP_TRY(hipStreamWaitEvent(s, d->ev_last, 0));
-  }
+  BANK_TRY(d->core.order_behind_last(s));
   const uint32_t W = d->n_captures, C = d->n_channels;
   DucParams P;
   {
-    std::lock_guard<std::mutex> g(d->mu);
+    std::lock_guard<std::mutex> g(d->core.mu);
     P.TA = (int)d->tapsA.size();
     P.TB = (int)d->tapsB.size();
-    P.LA = duc_la(P.TA, (int)d->R);
-    P.JA = P.TA > 0 ? ddc_packed_len(P.LA + 1) : 0;
-    P.JB = ddc_packed_len(P.TB);
+    P.LA = bank_branch_lookback(P.TA, (int)d->R);
+    P.JA = P.TA > 0 ? bank_packed_len(P.LA + 1) : 0;
+    P.JB = bank_packed_len(P.TB);
     if (d->dirty || d->clear_history)
     {
-      // records, channel lists, shifts, taps and a cleared history go to the device on `s`, ahead of this launch; the
-      // pinned staging buffers are rewritten only once the device has read the previous upload out of them
-      HIP_TRY(hipEventSynchronize(d->ev_upload));
-      memcpy(d->h_stage_chan, d->h_chan.data(), sizeof(DucChanDev) * C);
+      // records, channel lists, shifts, taps, a cleared history and cleared clip counters go to the device on `s`,
+      // ahead of this launch
+      BANK_TRY(d->core.staging_wait());
+      memcpy(d->h_stage_chan, d->h_chan.data(), sizeof(BankTuning) * C);
       uint32_t *off = d->h_stage_u32, *list = off + W + 1, *shift = list + C;
-      std::vector<uint32_t> count(W, 0u);
-      for (uint32_t c = 0; c < C; c++)
-      {
-        count[d->h_chan[c].capture]++;
-      }
-      off[0] = 0;
-      for (uint32_t w = 0; w < W; w++)
-      {
-        off[w + 1] = off[w] + count[w];
-        count[w] = off[w];
-      }
-      for (uint32_t c = 0; c < C; c++)
-      {
-        list[count[d->h_chan[c].capture]++] = c;
-      }
+      bank_channel_lists(d->h_chan.data(), C, W, off, list);
       memcpy(shift, d->h_shift.data(), sizeof(uint32_t) * W);
       memset(d->h_stage_taps, 0, sizeof(uint2) * (kDucJA + kDucJB));
       if (P.TA > 0)
       {
-        duc_pack_taps_a(d->tapsA, (int)d->R, d->h_stage_taps, P.JA);
+        bank_pack_branch_taps(d->tapsA.data(), P.TA, (int)d->R, d->h_stage_taps.p, P.JA);
       }
-      ddc_pack_taps(d->tapsB, d->h_stage_taps + kDucJA, P.JB);
-      HIP_TRY(hipMemcpyAsync(d->d_chan, d->h_stage_chan, sizeof(DucChanDev) * C, hipMemcpyHostToDevice, s));
+      bank_pack_taps(d->tapsB.data(), P.TB, d->h_stage_taps + kDucJA, P.JB);
+      HIP_TRY(hipMemcpyAsync(d->d_chan, d->h_stage_chan, sizeof(BankTuning) * C, hipMemcpyHostToDevice, s));
       HIP_TRY(hipMemcpyAsync(d->d_u32, d->h_stage_u32, sizeof(uint32_t) * (2 * (size_t)W + 1 + C), hipMemcpyHostToDevice, s));
       HIP_TRY(hipMemcpyAsync(d->d_taps, d->h_stage_taps, sizeof(uint2) * (kDucJA + kDucJB), hipMemcpyHostToDevice, s));
-      HIP_TRY(hipEventRecord(d->ev_upload, s));
+      BANK_TRY(d->core.staging_sent(s));
       if (d->clear_history)
       {
         HIP_TRY(hipMemsetAsync(d->d_hist[d->cur], 0, (size_t)C * kDucH * 2, s));
@@ -787,12 +607,12 @@ static int duc_launch(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_st
   if (e != hipSuccess)
   {
     // the counter and the history advance only with a launch that was accepted
-    std::lock_guard<std::mutex> g(d->mu);
+    std::lock_guard<std::mutex> g(d->core.mu);
     d->N = P.n0;
     return fail(HRFD_ENODEV, "k_duc launch failed: %s", hipGetErrorString(e));
   }
   d->cur ^= 1;
-  d->last_stream = s;
+  d->core.launched_on(s);
   return HRFD_OK;
 }
 
@@ -803,60 +623,29 @@ static int duc_check_call(hrfd_duc *d, const void *channels, uint64_t channel_st
   {
     return fail(HRFD_EINVAL, "%s: NULL argument", who);
   }
-  if (in_bytes < 2 || (in_bytes & 1u) != 0 || in_bytes > (1u << 25))
-  {
-    return fail(HRFD_EINVAL, "%s: in_bytes must be even, >= 2 and <= 2^25 (got %u)", who, in_bytes);
-  }
-  // one launch: gridDim.x * blockDim.x work-items must fit in 32 bits
-  if ((uint64_t)d->n_captures * ((in_bytes / 2u + hrfd::kDucTile - 1) / hrfd::kDucTile) + d->n_channels >
-      0xffffffffull / hrfd::kDucThreads)
-  {
-    return fail(HRFD_EINVAL, "%s: %u captures x %u bytes need more workgroups than one launch takes", who, d->n_captures,
-                in_bytes);
-  }
-  if (channel_stride < in_bytes || capture_stride < (uint64_t)d->R * in_bytes || (channel_stride & 1u) != 0 ||
-      ((uintptr_t)channels & 1u) != 0)
-  {
-    return fail(HRFD_EINVAL, "%s: strides shorter than a row, or an odd channel stride / address", who);
-  }
-  return HRFD_OK;
+  return hrfd::bank_check_call(who, "in_bytes", in_bytes, channels, channel_stride, 1u, capture_stride, d->R, d->n_captures,
+                               d->n_channels);
 }
 
 extern "C" int hrfd_duc_process_device(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_stride, uint32_t in_bytes,
                                        int8_t *d_captures, uint64_t capture_stride, void *stream)
 {
-  int rc = duc_check_call(d, d_channels, channel_stride, in_bytes, d_captures, capture_stride, "hrfd_duc_process_device");
-  if (rc != HRFD_OK)
-  {
-    return rc;
-  }
-  HIP_TRY(hipSetDevice(d->device));
-  return duc_launch(d, d_channels, channel_stride, in_bytes, d_captures, capture_stride,
-                    stream ? (hipStream_t)stream : d->stream);
+  BANK_TRY(duc_check_call(d, d_channels, channel_stride, in_bytes, d_captures, capture_stride, "hrfd_duc_process_device"));
+  HIP_TRY(hipSetDevice(d->core.device));
+  return duc_launch(d, d_channels, channel_stride, in_bytes, d_captures, capture_stride, d->core.stream_or_own(stream));
 }
 
 extern "C" int hrfd_duc_process(hrfd_duc *d, const int8_t *channels, uint32_t in_bytes, int8_t *captures)
 {
-  int rc = duc_check_call(d, channels, in_bytes, in_bytes, captures, d ? (uint64_t)d->R * in_bytes : 0, "hrfd_duc_process");
-  if (rc != HRFD_OK)
-  {
-    return rc;
-  }
-  HIP_TRY(hipSetDevice(d->device));
-  hipStream_t s = d->stream;
-  HIP_TRY(hipStreamSynchronize(s));
-  if (d->last_stream != s)
-  {
-    HIP_TRY(hipStreamSynchronize(d->last_stream));     // the staging buffers may still be read by the last launch
-  }
+  BANK_TRY(duc_check_call(d, channels, in_bytes, in_bytes, captures, d ? (uint64_t)d->R * in_bytes : 0, "hrfd_duc_process"));
+  HIP_TRY(hipSetDevice(d->core.device));
+  hipStream_t s = d->core.stream;
+  BANK_TRY(d->core.drain());
   const size_t in_total = (size_t)d->n_channels * in_bytes, out_total = (size_t)d->n_captures * d->R * in_bytes;
-  if ((rc = grow((void **)&d->d_in, &d->cap_in, in_total)) != HRFD_OK) return rc;
-  if ((rc = grow((void **)&d->d_out, &d->cap_out, out_total)) != HRFD_OK) return rc;
+  BANK_TRY(d->d_in.grow(in_total));
+  BANK_TRY(d->d_out.grow(out_total));
   HIP_TRY(hipMemcpyAsync(d->d_in, channels, in_total, hipMemcpyHostToDevice, s));
-  if ((rc = duc_launch(d, d->d_in, in_bytes, in_bytes, d->d_out, (uint64_t)d->R * in_bytes, s)) != HRFD_OK)
-  {
-    return rc;
-  }
+  BANK_TRY(duc_launch(d, d->d_in, in_bytes, in_bytes, d->d_out, (uint64_t)d->R * in_bytes, s));
   HIP_TRY(hipMemcpyAsync(captures, d->d_out, out_total, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return HRFD_OK;
@@ -874,32 +663,22 @@ extern "C" int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pc
     return fail(HRFD_EINVAL, "hrfd_duc_transmit: the modulator has %u channels, the DUC %u", mod->n_channels, d->n_channels);
   }
   const uint32_t in_bytes = 512u * n_per_channel;
-  int rc = duc_check_call(d, d_pcm, in_bytes, in_bytes, d_captures, capture_stride, "hrfd_duc_transmit");
-  if (rc != HRFD_OK)
+  BANK_TRY(duc_check_call(d, d_pcm, in_bytes, in_bytes, d_captures, capture_stride, "hrfd_duc_transmit"));
+  if (mod->device != d->core.device)
   {
-    return rc;
+    return fail(HRFD_EINVAL, "hrfd_duc_transmit: the modulator lives on device %d, the DUC on %d", mod->device,
+                d->core.device);
   }
-  if (mod->device != d->device)
-  {
-    return fail(HRFD_EINVAL, "hrfd_duc_transmit: the modulator lives on device %d, the DUC on %d", mod->device, d->device);
-  }
-  HIP_TRY(hipSetDevice(d->device));
-  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  HIP_TRY(hipSetDevice(d->core.device));
+  hipStream_t s = d->core.stream_or_own(stream);
   const size_t need = (size_t)d->n_channels * in_bytes;
-  if (need > d->cap_tx)
+  if (need > d->d_tx.cap)
   {
-    HIP_TRY(hipStreamSynchronize(d->last_stream));      // the last launch may still read the old buffer
-    if ((rc = grow((void **)&d->d_tx, &d->cap_tx, need)) != HRFD_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(d->core.last_stream));  // the last launch may still read the old buffer
+    BANK_TRY(d->d_tx.grow(need));
   }
   // the modulator overwrites the buffer the handle's last launch reads: behind it on the device
-  if (s != d->last_stream)
-  {
-    HIP_TRY(hipEventRecord(d->ev_last, d->last_stream));
-    HIP_TRY(hipStreamWaitEvent(s, d->ev_last, 0));
-  }
-  if ((rc = hrfd_mod_process_device(mod, d_pcm, n_per_channel, d->d_tx, s)) != HRFD_OK)
-  {
-    return rc;
-  }
+  BANK_TRY(d->core.order_behind_last(s));
+  BANK_TRY(hrfd_mod_process_device(mod, d_pcm, n_per_channel, d->d_tx, s));
   return duc_launch(d, d->d_tx, in_bytes, in_bytes, d_captures, capture_stride, s);
 }

@@ -21,7 +21,6 @@
 #include <string.h>
 
 #include <cmath>
-#include <mutex>
 #include <vector>
 
 namespace hrfd {
@@ -410,59 +409,30 @@ struct SpecBand
 
 struct hrfd_spec
 {
-  int device = 0;
+  hrfd::BankCore core;
   uint32_t n_captures = 0, R = 1;
   int L = 0;
   uint32_t N = 0;
   uint32_t target_wgs = 512;               // workgroups a launch aims for (two per CU fit beside each other)
-  hipStream_t stream = nullptr;
-  hipStream_t last_stream = nullptr;       // the stream of the last launch: the next one is ordered behind it
-  hipEvent_t ev_last = nullptr;
-  hipEvent_t ev_upload = nullptr;          // the last upload from the pinned staging buffers has been read
-  uint32_t *h_stage_win = nullptr;         // pinned: [N / 2]
-  hrfd::SpecBandDev *h_stage_bands = nullptr;   // pinned: [cap_stage_bands]
+  hrfd::PinnedBuf<uint32_t> h_stage_win;   // [N / 2]
+  hrfd::PinnedBuf<hrfd::SpecBandDev> h_stage_bands;   // [cap_stage_bands]
   size_t cap_stage_bands = 0;
 
-  std::mutex mu;                           // guards the host records (setters may come from another thread)
+  // host records, under core.mu
   std::vector<int16_t> window;
   std::vector<SpecBand> bands;
   bool dirty_win = true, dirty_bands = true;
 
-  uint32_t *d_win = nullptr, *d_tw = nullptr;
-  hrfd::SpecBandDev *d_bands = nullptr;
-  size_t cap_bands = 0;                    // bytes
-  int8_t *d_in = nullptr;                  // host-path staging
-  unsigned long long *d_power = nullptr, *d_band_power = nullptr;
-  uint8_t *d_present = nullptr;
-  size_t cap_in = 0, cap_power = 0, cap_band_power = 0, cap_present = 0;
+  hrfd::DevBuf<uint32_t> d_win, d_tw;
+  hrfd::DevBuf<hrfd::SpecBandDev> d_bands;
+  hrfd::DevBuf<int8_t> d_in;               // host-path staging
+  hrfd::DevBuf<unsigned long long> d_power, d_band_power;
+  hrfd::DevBuf<uint8_t> d_present;
 };
-
-static void spec_free(hrfd_spec *s)
-{
-  (void)hipSetDevice(s->device);
-  if (s->stream)
-  {
-    (void)hipStreamSynchronize(s->stream);
-  }
-  if (s->last_stream && s->last_stream != s->stream)
-  {
-    (void)hipStreamSynchronize(s->last_stream);
-  }
-  void *ptrs[] = {s->d_win, s->d_tw, s->d_bands, s->d_in, s->d_power, s->d_band_power, s->d_present};
-  for (void *p : ptrs)
-  {
-    if (p) (void)hipFree(p);
-  }
-  if (s->h_stage_win) (void)hipHostFree(s->h_stage_win);
-  if (s->h_stage_bands) (void)hipHostFree(s->h_stage_bands);
-  if (s->ev_last) (void)hipEventDestroy(s->ev_last);
-  if (s->ev_upload) (void)hipEventDestroy(s->ev_upload);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
 
 extern "C" int hrfd_spec_create(uint32_t n_captures, uint32_t decimation, uint32_t log2_n, int device, hrfd_spec **out)
 {
+  using namespace hrfd;
   if (out != nullptr)
   {
     *out = nullptr;
@@ -471,47 +441,29 @@ extern "C" int hrfd_spec_create(uint32_t n_captures, uint32_t decimation, uint32
   {
     return fail(HRFD_EINVAL, "hrfd_spec_create: need 1..65536 captures and a result pointer (got %u)", n_captures);
   }
-  if (decimation != 1 && decimation != 2 && decimation != 4 && decimation != 8)
+  BANK_TRY(bank_rate_ok("hrfd_spec_create", "decimation", decimation));
+  if (log2_n < (uint32_t)kSpecMinL || log2_n > (uint32_t)kSpecMaxL)
   {
-    return fail(HRFD_EINVAL, "hrfd_spec_create: decimation must be 1, 2, 4 or 8 (got %u)", decimation);
+    return fail(HRFD_EINVAL, "hrfd_spec_create: log2_n must be %d..%d (got %u)", kSpecMinL, kSpecMaxL, log2_n);
   }
-  if (log2_n < (uint32_t)hrfd::kSpecMinL || log2_n > (uint32_t)hrfd::kSpecMaxL)
-  {
-    return fail(HRFD_EINVAL, "hrfd_spec_create: log2_n must be %d..%d (got %u)", hrfd::kSpecMinL, hrfd::kSpecMaxL, log2_n);
-  }
-  if (hrfd_device_count() <= 0)
-  {
-    return fail(HRFD_ENODEV, "hrfd_spec_create: no HIP device visible (this library has no CPU path)");
-  }
-  if (device < 0)
-  {
-    HIP_TRY(hipGetDevice(&device));
-  }
-  HIP_TRY(hipSetDevice(device));
-  hrfd_spec *s = new hrfd_spec;
-  s->device = device;
+  hrfd_spec *s = nullptr;
+  BANK_TRY(bank_new("hrfd_spec_create", device, &s));
   s->n_captures = n_captures;
   s->R = decimation;
   s->L = (int)log2_n;
   s->N = 1u << log2_n;
-  hrfd::spec_hann(s->L, s->window);
+  spec_hann(s->L, s->window);
   std::vector<uint32_t> tw;
-  hrfd::spec_pass_tables(s->L, tw);
-  bool ok = tw.size() == (size_t)hrfd::spec_tw_dwords(s->L);
-  ok = ok && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipMalloc((void **)&s->d_win, sizeof(uint32_t) * (s->N / 2)) == hipSuccess;
-  ok = ok && hipMalloc((void **)&s->d_tw, sizeof(uint32_t) * tw.size()) == hipSuccess;
-  ok = ok && hipMemcpy(s->d_tw, tw.data(), sizeof(uint32_t) * tw.size(), hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&s->ev_last, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&s->ev_upload, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipHostMalloc((void **)&s->h_stage_win, sizeof(uint32_t) * (s->N / 2), hipHostMallocDefault) == hipSuccess;
+  spec_pass_tables(s->L, tw);
+  const bool ok = tw.size() == (size_t)spec_tw_dwords(s->L) && s->d_win.alloc(s->N / 2) && s->d_tw.alloc(tw.size()) &&
+                  hipMemcpy(s->d_tw, tw.data(), sizeof(uint32_t) * tw.size(), hipMemcpyHostToDevice) == hipSuccess &&
+                  s->h_stage_win.alloc(s->N / 2);
   if (!ok)
   {
     (void)hipGetLastError();
-    spec_free(s);
+    bank_free(s);
     return fail(HRFD_ENOMEM, "hrfd_spec_create: device allocation failed");
   }
-  s->last_stream = s->stream;
   *out = s;
   return HRFD_OK;
 }
@@ -520,7 +472,7 @@ extern "C" int hrfd_spec_destroy(hrfd_spec *s)
 {
   if (s != nullptr)
   {
-    spec_free(s);
+    hrfd::bank_free(s);
   }
   return HRFD_OK;
 }
@@ -531,7 +483,7 @@ extern "C" int hrfd_spec_set_window(hrfd_spec *s, const int16_t *w)
   {
     return fail(HRFD_EINVAL, "hrfd_spec_set_window: NULL handle");
   }
-  std::lock_guard<std::mutex> g(s->mu);
+  std::lock_guard<std::mutex> g(s->core.mu);
   if (w == nullptr)
   {
     hrfd::spec_hann(s->L, s->window);
@@ -555,7 +507,7 @@ extern "C" int hrfd_spec_set_band(hrfd_spec *s, uint32_t band, uint32_t capture,
   {
     return fail(HRFD_EINVAL, "hrfd_spec_set_band: bad handle or capture, first_bin >= N, or n_bins not in 1..N");
   }
-  std::lock_guard<std::mutex> g(s->mu);
+  std::lock_guard<std::mutex> g(s->core.mu);
   if (band > s->bands.size() || band >= HRFD_SPEC_MAX_BANDS)
   {
     return fail(HRFD_EINVAL, "hrfd_spec_set_band: band %u, the handle has %zu (band == K appends; at most %u)", band,
@@ -580,7 +532,7 @@ extern "C" int hrfd_spec_clear_bands(hrfd_spec *s)
   {
     return fail(HRFD_EINVAL, "hrfd_spec_clear_bands: NULL handle");
   }
-  std::lock_guard<std::mutex> g(s->mu);
+  std::lock_guard<std::mutex> g(s->core.mu);
   s->bands.clear();
   s->dirty_bands = true;
   return HRFD_OK;
@@ -592,7 +544,7 @@ extern "C" int hrfd_spec_n_bands(hrfd_spec *s, uint32_t *k)
   {
     return fail(HRFD_EINVAL, "hrfd_spec_n_bands: NULL argument");
   }
-  std::lock_guard<std::mutex> g(s->mu);
+  std::lock_guard<std::mutex> g(s->core.mu);
   *k = (uint32_t)s->bands.size();
   return HRFD_OK;
 }
@@ -619,7 +571,7 @@ static int spec_check_call(hrfd_spec *s, const void *captures, uint64_t capture_
   }
   bool need;
   {
-    std::lock_guard<std::mutex> g(s->mu);
+    std::lock_guard<std::mutex> g(s->core.mu);
     need = !s->bands.empty();
   }
   if (need && (band_power == nullptr || present == nullptr))
@@ -635,19 +587,14 @@ static int spec_launch(hrfd_spec *s, const int8_t *d_captures, uint64_t capture_
                        hipStream_t st)
 {
   using namespace hrfd;
-  if (st != s->last_stream)
-  {
-    HIP_TRY(hipEventRecord(s->ev_last, s->last_stream));
-    HIP_TRY(hipStreamWaitEvent(st, s->ev_last, 0));
-  }
+  BANK_TRY(s->core.order_behind_last(st));
   uint32_t K;
   {
-    std::lock_guard<std::mutex> g(s->mu);
+    std::lock_guard<std::mutex> g(s->core.mu);
     K = std::min((uint32_t)s->bands.size(), max_bands);   // bands appended since the caller sized its outputs wait a call
     if (s->dirty_win || s->dirty_bands)
     {
-      // the pinned staging buffers are rewritten only once the device has read the previous upload out of them
-      HIP_TRY(hipEventSynchronize(s->ev_upload));
+      BANK_TRY(s->core.staging_wait());
       if (s->dirty_win)
       {
         memcpy(s->h_stage_win, s->window.data(), sizeof(int16_t) * s->N);
@@ -658,25 +605,25 @@ static int spec_launch(hrfd_spec *s, const int8_t *d_captures, uint64_t capture_
       {
         if (K > s->cap_stage_bands)
         {
-          HIP_TRY(hipStreamSynchronize(s->last_stream));   // the last band kernel may still read the old table
-          if (s->h_stage_bands) (void)hipHostFree(s->h_stage_bands);
-          s->h_stage_bands = nullptr;
+          HIP_TRY(hipStreamSynchronize(s->core.last_stream));   // the last band kernel may still read the old table
           s->cap_stage_bands = 0;
           const size_t cap = std::max<size_t>(64, 2 * (size_t)K);
-          HIP_TRY(hipHostMalloc((void **)&s->h_stage_bands, sizeof(SpecBandDev) * cap, hipHostMallocDefault));
+          if (!s->h_stage_bands.alloc(cap))
+          {
+            return fail(HRFD_ENODEV, "hrfd_spec: no pinned memory for %zu bands: %s", cap, hipGetErrorString(hipGetLastError()));
+          }
           s->cap_stage_bands = cap;
-          int rc = grow((void **)&s->d_bands, &s->cap_bands, sizeof(SpecBandDev) * cap);
-          if (rc != HRFD_OK) return rc;
+          BANK_TRY(s->d_bands.grow(sizeof(SpecBandDev) * cap));
         }
         for (uint32_t b = 0; b < K; b++)
         {
-          s->h_stage_bands[b] = SpecBandDev{s->bands[b].capture, s->bands[b].first, s->bands[b].n_bins, 0u,
+          s->h_stage_bands.p[b] = SpecBandDev{s->bands[b].capture, s->bands[b].first, s->bands[b].n_bins, 0u,
                                             (unsigned long long)s->bands[b].threshold};
         }
         HIP_TRY(hipMemcpyAsync(s->d_bands, s->h_stage_bands, sizeof(SpecBandDev) * K, hipMemcpyHostToDevice, st));
       }
       s->dirty_bands = K < s->bands.size();
-      HIP_TRY(hipEventRecord(s->ev_upload, st));
+      BANK_TRY(s->core.staging_sent(st));
     }
   }
   SpecParams P;
@@ -714,57 +661,42 @@ static int spec_launch(hrfd_spec *s, const int8_t *d_captures, uint64_t capture_
   {
     return fail(HRFD_ENODEV, "k_spec launch failed: %s", hipGetErrorString(e));
   }
-  s->last_stream = st;
+  s->core.launched_on(st);
   return HRFD_OK;
 }
 
 extern "C" int hrfd_spec_process_device(hrfd_spec *s, const int8_t *d_captures, uint64_t capture_stride, uint32_t n_frames,
                                         uint64_t *d_power, uint64_t *d_band_power, uint8_t *d_present, void *stream)
 {
-  int rc = spec_check_call(s, d_captures, capture_stride, n_frames, d_power, d_band_power, d_present, "hrfd_spec_process_device");
-  if (rc != HRFD_OK)
-  {
-    return rc;
-  }
-  HIP_TRY(hipSetDevice(s->device));
+  BANK_TRY(spec_check_call(s, d_captures, capture_stride, n_frames, d_power, d_band_power, d_present, "hrfd_spec_process_device"));
+  HIP_TRY(hipSetDevice(s->core.device));
   return spec_launch(s, d_captures, capture_stride, n_frames, (unsigned long long *)d_power, (unsigned long long *)d_band_power,
-                     d_present, 0xffffffffu, stream ? (hipStream_t)stream : s->stream);
+                     d_present, 0xffffffffu, s->core.stream_or_own(stream));
 }
 
 extern "C" int hrfd_spec_process(hrfd_spec *s, const int8_t *captures, uint32_t n_frames, uint64_t *power, uint64_t *band_power,
                                  uint8_t *present)
 {
-  int rc = spec_check_call(s, captures, s ? 2ull * s->N * n_frames : 0, n_frames, power, band_power, present, "hrfd_spec_process");
-  if (rc != HRFD_OK)
-  {
-    return rc;
-  }
-  HIP_TRY(hipSetDevice(s->device));
-  hipStream_t st = s->stream;
-  HIP_TRY(hipStreamSynchronize(st));
-  if (s->last_stream != st)
-  {
-    HIP_TRY(hipStreamSynchronize(s->last_stream));       // the staging buffers may still be read by the last launch
-  }
+  BANK_TRY(spec_check_call(s, captures, s ? 2ull * s->N * n_frames : 0, n_frames, power, band_power, present, "hrfd_spec_process"));
+  HIP_TRY(hipSetDevice(s->core.device));
+  hipStream_t st = s->core.stream;
+  BANK_TRY(s->core.drain());
   uint32_t K;
   {
-    std::lock_guard<std::mutex> g(s->mu);
+    std::lock_guard<std::mutex> g(s->core.mu);
     K = (uint32_t)s->bands.size();
   }
   const size_t row = 2 * (size_t)s->N * n_frames, in_total = row * s->n_captures;
   const size_t p_total = sizeof(uint64_t) * (size_t)s->n_captures * s->N;
-  if ((rc = grow((void **)&s->d_in, &s->cap_in, in_total)) != HRFD_OK) return rc;
-  if ((rc = grow((void **)&s->d_power, &s->cap_power, p_total)) != HRFD_OK) return rc;
+  BANK_TRY(s->d_in.grow(in_total));
+  BANK_TRY(s->d_power.grow(p_total));
   if (K > 0)
   {
-    if ((rc = grow((void **)&s->d_band_power, &s->cap_band_power, sizeof(uint64_t) * K)) != HRFD_OK) return rc;
-    if ((rc = grow((void **)&s->d_present, &s->cap_present, K)) != HRFD_OK) return rc;
+    BANK_TRY(s->d_band_power.grow(sizeof(uint64_t) * K));
+    BANK_TRY(s->d_present.grow(K));
   }
   HIP_TRY(hipMemcpyAsync(s->d_in, captures, in_total, hipMemcpyHostToDevice, st));
-  if ((rc = spec_launch(s, s->d_in, row, n_frames, s->d_power, s->d_band_power, s->d_present, K, st)) != HRFD_OK)
-  {
-    return rc;
-  }
+  BANK_TRY(spec_launch(s, s->d_in, row, n_frames, s->d_power, s->d_band_power, s->d_present, K, st));
   HIP_TRY(hipMemcpyAsync(power, s->d_power, p_total, hipMemcpyDeviceToHost, st));
   if (K > 0)
   {

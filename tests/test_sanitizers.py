@@ -28,6 +28,23 @@ def test_txring_under_sanitizers(tmp_path, san):
     assert r.returncode == 0 and "san_txring ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
 
 
+def test_bank_core_under_sanitizers(tmp_path):
+    """The HIP-free part of the bank core (hackrfdiags_amd/csrc/hrfd_bank.h: tap check and packing, the tuning record, the
+    DUC's channel lists) compiled into tests/cpp/san_bank.cc under -fsanitize=address,undefined and run."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "san_bank")
+    cmd = ["g++", "-x", "c++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+           os.path.join(HERE, "cpp", "san_bank.cc")]
+    b = subprocess.run(cmd, capture_output=True, text=True, cwd=os.path.join(HERE, "cpp"))
+    if b.returncode != 0 and ("cannot find" in b.stderr or "unrecognized" in b.stderr):
+        pytest.skip("this toolchain has no runtime for -fsanitize=address,undefined")
+    assert b.returncode == 0, b.stderr[-2000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0 and "san_bank ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
+
+
 SHIM = os.path.join(os.path.dirname(HERE), "hackrfdiags_amd", "csrc", "shim")
 
 
