@@ -54,6 +54,9 @@ static int fail(int code, const char *fmt, ...)
     }                                                                                    \
   } while (0)
 
+#include "hrfd_buf.h"
+#include "hrfd_rx_plan.h"
+
 extern "C" const char *hrfd_last_error(void) { return g_err; }
 extern "C" int hrfd_version(void) { return HRFD_VERSION; }
 
@@ -191,10 +194,6 @@ extern "C" int hrfd_q15_table(const char *name, int16_t *out, int cap)
 }
 
 // ------------------------------------------------------------------ rx handle
-#ifndef HRFD_BANK_XCD_ORDER
-#define HRFD_BANK_XCD_ORDER 0      /* 1: the mixed bank's WBFM channels on the even XCDs -- MEASURED, NOTHING (profiles/r5_bank_order_ab_NOTHING.txt) */
-#endif
-
 struct hrfd_rx
 {
   int device = 0;
@@ -208,49 +207,43 @@ struct hrfd_rx
   bool cfg_dirty = true;
   std::vector<std::pair<uint32_t, int>> pending_resets;   // (channel, mode)
 
-  ChanCfg *d_cfg = nullptr;
-  ChanState *d_state = nullptr;
-  ChanState *d_state_out = nullptr;
-  float *d_lut = nullptr;
-  uint8_t *d_atcorr = nullptr;         // arithmetic atan2 (theta_arith): correction bytes, 1/a
-  float *d_atinv = nullptr;
-  uint8_t *d_atcorr2 = nullptr;        // first-octant table atan2 (theta_tab): correction bytes, T0
-  float *d_att0 = nullptr;
+  // device memory: every buffer is owned here and freed with the handle (DevBuf)
+  DevBuf<ChanCfg> d_cfg;
+  DevBuf<ChanState> d_state, d_state_out;
+  DevBuf<float> d_lut;
+  DevBuf<uint8_t> d_atcorr;            // arithmetic atan2 (theta_arith): correction bytes, 1/a
+  DevBuf<float> d_atinv;
+  DevBuf<uint8_t> d_atcorr2;           // first-octant table atan2 (theta_tab): correction bytes, T0
+  DevBuf<float> d_att0;
   bool tab_ok = false;                 // its corrections fit: k_rx_wbfm_flow may run
-  uint32_t *d_atquad = nullptr;        // first-quadrant table with embedded corrections (theta_quad: the re-split WBFM flow kernel)
+  DevBuf<uint32_t> d_atquad;           // first-quadrant table with embedded corrections (theta_quad: the re-split WBFM flow kernel)
   bool quad_ok = false;
   bool arith_ok = false;               // corrections fit: k_rx_wbfm computes theta instead of gathering it
   int atan_mode = -1;                  // test hook: -1 auto, 0 force the table gather, 1 require arithmetic
-  int32_t *d_dbfs = nullptr;
-  uint32_t *d_counters = nullptr;       // [kNumDevCounters] + a second set of the per-launch counters [kCntSticky]
+  DevBuf<int32_t> d_dbfs;
+  DevBuf<uint32_t> d_counters;          // [kNumDevCounters] + a second set of the per-launch counters [kCntSticky]
   uint32_t *d_local = nullptr;          // the per-launch counters of the latest launch (set 0 = d_counters, set 1 behind it)
   int parity = 0;
-  uint32_t *d_lists = nullptr;         // [10][n_channels] channel ids grouped by mode; list 6: every channel that is not WBFM,
+  DevBuf<uint32_t> d_lists;            // [10][n_channels] channel ids grouped by mode; list 6: every channel that is not WBFM,
                                        // list 7: the AM and SSB channels, list 9: every channel but those in mode NONE
   uint32_t list_count[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t *d_sub_lists = nullptr;     // the same for a launch over a subset of the channels (replay of failed channels);
+  DevBuf<uint32_t> d_sub_lists;        // the same for a launch over a subset of the channels (replay of failed channels);
                                        // list 6 there: the subset itself
-  uint32_t *d_chan = nullptr;          // [4][n_channels]: chan_fail, chan_poison, chan_expired, chan_arrived (EpilogueParams)
+  DevBuf<uint32_t> d_chan;             // [4][n_channels]: chan_fail, chan_poison, chan_expired, chan_arrived (EpilogueParams)
   std::vector<uint32_t> h_fail;        // chan_fail of the latest synchronised launch
 
-  // per-call scratch, grown on demand (units = channels * blocks)
-  size_t cap_units = 0;
-  uint8_t *d_present = nullptr;
-  uint32_t *d_magnitude = nullptr;
-  float *d_chk_pub = nullptr;
-  float *d_chk_spec = nullptr;
-  int16_t *d_ssb_iq = nullptr;         // 8 kS/s I/Q of the SSB channels, [units][2][npcm]
-  size_t cap_ssb = 0;
+  // per-call scratch, grown on demand (units = channels * blocks); the four per-unit buffers grow together
+  DevBuf<uint8_t> d_present;
+  DevBuf<uint32_t> d_magnitude;
+  DevBuf<float> d_chk_pub, d_chk_spec;
+  size_t unit_cap() const { return std::min({d_present.cap, d_magnitude.cap / 4, d_chk_pub.cap / 4, d_chk_spec.cap / 4}); }
+  DevBuf<int16_t> d_ssb_iq;            // 8 kS/s I/Q of the SSB channels, [units][2][npcm]
 
   // staging for the host-buffer entry
-  size_t cap_iq = 0, cap_pcm = 0, cap_iq256 = 0;
-  int8_t *d_iq = nullptr;
-  int16_t *d_pcm = nullptr;
-  int8_t *d_iq256 = nullptr;
-  size_t cap_npcm = 0, cap_allowed = 0, cap_mag_out = 0;
-  uint32_t *d_npcm = nullptr;
-  uint8_t *d_allowed = nullptr;
-  uint32_t *d_mag_out = nullptr;
+  DevBuf<int8_t> d_iq, d_iq256;
+  DevBuf<int16_t> d_pcm;
+  DevBuf<uint32_t> d_npcm, d_mag_out;
+  DevBuf<uint8_t> d_allowed;
   uint32_t replays = 0;                // launches redone on the exact path (diagnostic)
   uint32_t total_repairs = 0;          // de-emphasis tiles repaired in place since creation
 
@@ -260,8 +253,7 @@ struct hrfd_rx
   uint32_t ev_every = 1, ev_seen = 0;                     // every ev_every-th launch is bracketed (hrfd_rx_debug_timing_every)
 
   // test hooks
-  unsigned long long *d_dbg = nullptr;  // optional phase stamps (hrfd_rx_debug_stamps)
-  size_t dbg_cap = 0;
+  DevBuf<unsigned long long> d_dbg;     // optional phase stamps (hrfd_rx_debug_stamps)
   int warm = kWarm;
   int stagger = 4;
   int run_len = 0;                     // test hook: blocks per workgroup run of k_rx_wbfm (0 = automatic)
@@ -277,7 +269,7 @@ struct hrfd_rx
   // The first block of another length takes it off the grid, for good: RagState per channel, every call on k_rx_ragged.
   bool offgrid = false;
   bool rag_built = false;              // k_rag_expand has run (ChanState -> RagState)
-  RagState *d_rag = nullptr;
+  DevBuf<RagState> d_rag;
   uint64_t ragged_launches = 0;        // launches that ran on k_rx_ragged (diagnostic: hrfd_rx_debug_ragged)
 };
 
@@ -289,19 +281,12 @@ static int rx_free(hrfd_rx *h)
   }
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  void *ptrs[] = {h->d_cfg, h->d_state, h->d_state_out, h->d_lut, h->d_atcorr, h->d_atinv, h->d_atcorr2, h->d_att0, h->d_atquad, h->d_dbfs, h->d_counters,
-                  h->d_lists, h->d_sub_lists, h->d_chan, h->d_present, h->d_magnitude, h->d_chk_pub, h->d_chk_spec,
-                  h->d_iq, h->d_pcm, h->d_iq256, h->d_npcm, h->d_allowed, h->d_mag_out, h->d_ssb_iq, h->d_dbg, h->d_rag};
-  for (void *p : ptrs)
-  {
-    if (p) (void)hipFree(p);
-  }
   for (hipEvent_t e : h->ev)
   {
     (void)hipEventDestroy(e);
   }
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;                            // with every buffer it owns
   return HRFD_OK;
 }
 
@@ -347,33 +332,20 @@ extern "C" int hrfd_rx_create(uint32_t n_channels, int device, hrfd_rx **out)
   }
   h->h_cfg.assign(n_channels, default_cfg());
   int rc = HRFD_OK;
-  auto alloc = [&](void **p, size_t bytes) -> bool {
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess)
-    {
-      rc = fail(HRFD_ENOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-      return false;
-    }
-    return true;
-  };
-  bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && alloc((void **)&h->d_cfg, sizeof(ChanCfg) * n_channels);
-  ok = ok && alloc((void **)&h->d_state, sizeof(ChanState) * n_channels);
-  ok = ok && alloc((void **)&h->d_state_out, sizeof(ChanState) * n_channels);
-  ok = ok && alloc((void **)&h->d_lut, sizeof(float) * 65536);
-  ok = ok && alloc((void **)&h->d_atcorr, kCorrBytes);
-  ok = ok && alloc((void **)&h->d_atinv, sizeof(float) * kInvEntries);
-  ok = ok && alloc((void **)&h->d_atcorr2, kCorrBytes);
-  ok = ok && alloc((void **)&h->d_att0, sizeof(float) * kCorrBytes);
-  ok = ok && alloc((void **)&h->d_atquad, sizeof(uint32_t) * kQuadDwords);
-  ok = ok && alloc((void **)&h->d_dbfs, sizeof(int32_t) * 257);
-  ok = ok && alloc((void **)&h->d_counters, sizeof(uint32_t) * (kNumDevCounters + kCntSticky));
-  ok = ok && alloc((void **)&h->d_lists, sizeof(uint32_t) * 10 * n_channels);
-  ok = ok && alloc((void **)&h->d_sub_lists, sizeof(uint32_t) * 10 * n_channels);
-  ok = ok && alloc((void **)&h->d_chan, sizeof(uint32_t) * 4 * n_channels);
-  if (!ok)
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
   {
-    if (rc == HRFD_OK) rc = fail(HRFD_ENODEV, "hrfd_rx_create: stream creation failed");
+    rc = fail(HRFD_ENODEV, "hrfd_rx_create: stream creation failed");
+  }
+  else if (!(h->d_cfg.alloc(n_channels) && h->d_state.alloc(n_channels) && h->d_state_out.alloc(n_channels) && h->d_lut.alloc(65536) &&
+             h->d_atcorr.alloc(kCorrBytes) && h->d_atinv.alloc(kInvEntries) && h->d_atcorr2.alloc(kCorrBytes) && h->d_att0.alloc(kCorrBytes) &&
+             h->d_atquad.alloc(kQuadDwords) && h->d_dbfs.alloc(257) && h->d_counters.alloc(kNumDevCounters + kCntSticky) &&
+             h->d_lists.alloc((size_t)kRxLists * n_channels) && h->d_sub_lists.alloc((size_t)kRxLists * n_channels) &&
+             h->d_chan.alloc((size_t)4 * n_channels)))
+  {
+    rc = HRFD_ENOMEM;                                      // (the text is the failed allocation's)
+  }
+  if (rc != HRFD_OK)
+  {
     rx_free(h);
     return rc;
   }
@@ -413,8 +385,8 @@ extern "C" int hrfd_rx_create(uint32_t n_channels, int device, hrfd_rx **out)
   if (e == hipSuccess) e = hipMemcpy(h->d_atinv, inv, sizeof(inv), hipMemcpyHostToDevice);
   if (e == hipSuccess)
   {
-    hipLaunchKernelGGL(k_build_atan_corr<false>, dim3((kCorrBytes + 255) / 256), dim3(256), 0, 0, h->d_lut, h->d_atinv,
-                       h->d_atcorr, h->d_counters + kCntScratch);
+    hipLaunchKernelGGL(k_build_atan_corr<false>, dim3((kCorrBytes + 255) / 256), dim3(256), 0, 0, h->d_lut.p, h->d_atinv.p,
+                       h->d_atcorr.p, h->d_counters + kCntScratch);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(&bad, h->d_counters + kCntScratch, sizeof(bad), hipMemcpyDeviceToHost);
@@ -435,8 +407,8 @@ extern "C" int hrfd_rx_create(uint32_t n_channels, int device, hrfd_rx **out)
   }
   if (e == hipSuccess)
   {
-    hipLaunchKernelGGL(k_build_atan_corr<true>, dim3((kCorrBytes + 255) / 256), dim3(256), 0, 0, h->d_lut, h->d_att0,
-                       h->d_atcorr2, h->d_counters + kCntScratch);
+    hipLaunchKernelGGL(k_build_atan_corr<true>, dim3((kCorrBytes + 255) / 256), dim3(256), 0, 0, h->d_lut.p, h->d_att0.p,
+                       h->d_atcorr2.p, h->d_counters + kCntScratch);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(&bad2, h->d_counters + kCntScratch, sizeof(bad2), hipMemcpyDeviceToHost);
@@ -527,24 +499,6 @@ extern "C" int hrfd_rx_reset_demod(hrfd_rx *h, uint32_t channel, int mode)
   return for_channels(h, channel, [&](uint32_t c) { h->pending_resets.push_back({c, mode}); });
 }
 
-static int grow(void **p, size_t *cap, size_t need)
-{
-  if (need <= *cap && *p != nullptr)
-  {
-    return HRFD_OK;
-  }
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  hipError_t e = hipMalloc(p, need);
-  if (e != hipSuccess)
-  {
-    *cap = 0;
-    return fail(HRFD_ENOMEM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-  }
-  *cap = need;
-  return HRFD_OK;
-}
-
 // apply queued X::resetDemodulator calls to the device state
 static int apply_resets(hrfd_rx *h, hipStream_t s, std::vector<std::pair<uint32_t, int>> &resets)
 {
@@ -609,233 +563,117 @@ struct LaunchOpts
   const std::vector<uint32_t> *subset = nullptr;   // launch for these channels only (ascending ids), nullptr = all
 };
 
-static int rx_launch(hrfd_rx *h, const int8_t *d_iq, uint64_t channel_stride, uint32_t block_bytes,
-                     uint32_t n_blocks, uint32_t gain_db, int16_t *d_pcm, uint32_t *d_n_pcm,
-                     uint32_t *d_magnitude, uint8_t *d_allowed, int8_t *d_iq256, hipStream_t s,
-                     const LaunchOpts &opt)
+// the arguments of rx_launch, for its steps
+struct RxCall
 {
-  if (h == nullptr || d_iq == nullptr || d_pcm == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_rx_process: NULL handle or buffer");
-  }
-  // Lengths.  The reference takes any byteCount (IqDataProcessor.cc:926, DataConsumer.cc:229-241: short transfers are
-  // passed on); what it cannot take is refused here: more than its fixed arrays hold (DataConsumer clips to 262144
-  // before the call, DataConsumer.cc:229-233; the demodulators' members hold 32768 bytes) and odd counts (its Q loop
-  // then reads bufferPtr[byteCount], IqDataProcessor.cc:474: the caller rounds up, as hrfd_shim.cc does).
-  const uint32_t max_bytes = opt.src256 ? 32768u : HRFD_BLOCK_BYTES;
-  if (block_bytes == 0 || (block_bytes & 1u) != 0 || block_bytes > max_bytes)
-  {
-    return fail(HRFD_EINVAL, "%s must be even, > 0 and <= %u (got %u)", opt.src256 ? "bytes_per_channel" : "block_bytes",
-                max_bytes, block_bytes);
-  }
-  // the streaming kernels take whole 1 KiB chunks (inner API: 128 bytes) on a handle that never left the grid
-  const bool ragged = h->offgrid || (block_bytes % (opt.src256 ? 128u : 1024u)) != 0;
-  if (n_blocks == 0 || opt.out_b0 + n_blocks > opt.out_blocks)
-  {
-    return fail(HRFD_EINVAL, "bad block count");
-  }
-  if (channel_stride < (uint64_t)block_bytes * n_blocks)
-  {
-    return fail(HRFD_EINVAL, "channel_stride smaller than n_blocks*block_bytes");
-  }
-  if ((uint64_t)block_bytes * n_blocks > 0x7fffffffull)
-  {
-    // the kernels address a channel's input through a 32-bit buffer descriptor (num_records, byte offsets)
-    return fail(HRFD_EINVAL, "n_blocks*block_bytes = %llu exceeds 2^31 - 1 bytes per channel and call",
-                (unsigned long long)block_bytes * n_blocks);
-  }
-  HIP_TRY(hipSetDevice(h->device));
+  const int8_t *d_iq;
+  uint64_t channel_stride;
+  uint32_t block_bytes, n_blocks, gain_db;
+  int16_t *d_pcm;
+  uint32_t *d_n_pcm, *d_magnitude;
+  uint8_t *d_allowed;
+  int8_t *d_iq256;
+  hipStream_t s;
+  const LaunchOpts &opt;
+};
 
-  const uint32_t n256 = opt.src256 ? block_bytes / 2 : block_bytes / 16;
-  const uint32_t halo_unit = opt.src256 ? 2u : 16u;   // input bytes per 256 kS/s sample
-  // De-emphasis tiles of kTile samples end at n256.  A lane starts warm_tiles tiles early from a
-  // seed summed over seed_terms tiles, so in a block that has to re-derive its history (the first
-  // block of a workgroup's run when b > 0) the first `sac` tiles cannot be started properly: they
-  // are sacrificial, and tile `sac` must begin at or before the cross-block check position
-  // -(kNeedHist + 1), the first sample the integer stages' history is built from.
-  const int warm_tiles = (h->warm >= kWarm) ? kWarmTiles : std::min(kWarmTiles, h->warm / 128);
-  const int seed_terms = (h->warm >= kWarm) ? kSeedTerms : 0;
-  const int sac = warm_tiles + seed_terms;
-  const int ntiles = ((int)n256 + kNeedHist + 1 + kTile - 1) / kTile + sac;
-  const int origin = (int)n256 - ntiles * kTile;
-  const int hal = (-origin + 63) / 64 * 64;
-  if (!ragged && ntiles > kMaxTiles)
-  {
-    return fail(HRFD_EINVAL, "internal: %d de-emphasis tiles exceed %d", ntiles, kMaxTiles);
-  }
-  if (!ragged && hal > kMaxHal)
-  {
-    return fail(HRFD_EINVAL, "internal: history %d exceeds %d", hal, kMaxHal);
-  }
-  if (!ragged && n_blocks > 1 && (uint32_t)(hal + 64) * halo_unit > block_bytes)
-  {
-    return fail(HRFD_EINVAL, "blocks of %u bytes are too short for a multi-block call "
-                "(need >= %u); submit them one per call", block_bytes, (uint32_t)(hal + 64) * halo_unit);
-  }
-  if (opt.serial && n_blocks != 1)
-  {
-    return fail(HRFD_ESTATE, "internal: serial replay needs n_blocks == 1");
-  }
-
-  // configuration snapshot
-  uint32_t sub_count[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  std::vector<uint32_t> sub_lists;
-  std::vector<std::pair<uint32_t, int>> resets;
+// The configuration snapshot, under the handle's lock: the queued resets are taken over, the per-mode lists are rebuilt
+// and uploaded when a setter has run, and a subset gets lists of its own (sub_count).
+static int rx_snapshot(hrfd_rx *h, const RxCall &c, uint32_t sub_count[kRxLists], std::vector<std::pair<uint32_t, int>> &resets)
+{
+  const std::vector<uint32_t> *const subset = c.opt.subset;
+  std::vector<uint32_t> lists;
   {
     std::lock_guard<std::mutex> g(h->mu);
     resets.swap(h->pending_resets);
     if (h->cfg_dirty)
     {
-      std::vector<uint32_t> lists((size_t)10 * h->n_channels);
-      uint32_t cnt[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      for (uint32_t c = 0; c < h->n_channels; c++)
-      {
-        const int m = h->h_cfg[c].mode;
-        lists[(size_t)m * h->n_channels + cnt[m]++] = c;
-        if (m != HRFD_MODE_WBFM)
-        {
-          lists[(size_t)6 * h->n_channels + cnt[6]++] = c;
-        }
-        if (m == HRFD_MODE_AM || m == HRFD_MODE_LSB || m == HRFD_MODE_USB)
-        {
-          lists[(size_t)7 * h->n_channels + cnt[7]++] = c;
-        }
-        if (m != HRFD_MODE_NONE)
-        {
-          lists[(size_t)9 * h->n_channels + cnt[9]++] = c;   // list 9: every channel that has a demodulator (k_rx_flow_bank)
-        }
-      }
-      // List 9 runs as ONE launch, position p on XCD p % 8 (map_unit), a workgroup per channel; the workgroups on the XCDs
-      // with odd numbers are 3-5 % slower than the others in most launches (profiles/r5_xcd_swap_experiment.txt) and in the
-      // mixed bank the WBFM workgroups end ~10 us behind the FIR kinds'.  -DHRFD_BANK_XCD_ORDER=1 puts the WBFM channels on
-      // the even positions: MEASURED AND LEFT OFF -- sixteen WBFM workgroups on an XCD instead of eight run slower by what
-      // the placement was to gain (the XCDs' clocks are managed one by one), the bank takes the same time
-      // (profiles/r5_bank_order_ab_NOTHING.txt).  Which position a channel has changes nothing it computes.
-      {
-        std::vector<uint32_t> heavy, light;
-        for (uint32_t i = 0; i < cnt[9]; i++)
-        {
-          const uint32_t c = lists[(size_t)9 * h->n_channels + i];
-          (h->h_cfg[c].mode == HRFD_MODE_WBFM ? heavy : light).push_back(c);
-        }
-        size_t ih = 0, il = 0;
-        for (uint32_t p = 0; p < cnt[9] && HRFD_BANK_XCD_ORDER; p++)
-        {
-          const bool want_heavy = (p & 1u) == 0u;
-          const bool take_heavy = (want_heavy && ih < heavy.size()) || il >= light.size();
-          lists[(size_t)9 * h->n_channels + p] = take_heavy ? heavy[ih++] : light[il++];
-        }
-      }
-      memcpy(h->list_count, cnt, sizeof(cnt));
-      h->wbfm_max_threshold = INT32_MIN;
-      for (uint32_t c = 0; c < h->n_channels; c++)
-      {
-        if (h->h_cfg[c].mode != HRFD_MODE_NONE)
-        {
-          h->wbfm_max_threshold = std::max(h->wbfm_max_threshold, h->h_cfg[c].threshold);
-        }
-      }
+      lists.assign((size_t)kRxLists * h->n_channels, 0u);
+      rx_build_lists(h->h_cfg.data(), h->n_channels, false, nullptr, 0, lists.data(), h->list_count);
+      h->wbfm_max_threshold = rx_max_threshold(h->h_cfg.data(), h->n_channels);
       // synchronous uploads: the host vectors are only valid under the lock
-      HIP_TRY(hipStreamSynchronize(s));
+      HIP_TRY(hipStreamSynchronize(c.s));
       HIP_TRY(hipMemcpy(h->d_cfg, h->h_cfg.data(), sizeof(ChanCfg) * h->n_channels, hipMemcpyHostToDevice));
       HIP_TRY(hipMemcpy(h->d_lists, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice));
       h->cfg_dirty = false;
     }
-    if (opt.subset != nullptr)
+    if (subset != nullptr)
     {
-      // per-mode lists of the subset (list 6: the subset itself); only the modes are read under the lock
-      sub_lists.resize((size_t)10 * h->n_channels);
-      for (uint32_t c : *opt.subset)
-      {
-        const int m = h->h_cfg[c].mode;
-        sub_lists[(size_t)m * h->n_channels + sub_count[m]++] = c;
-        sub_lists[(size_t)6 * h->n_channels + sub_count[6]++] = c;
-        if (m == HRFD_MODE_AM || m == HRFD_MODE_LSB || m == HRFD_MODE_USB)
-        {
-          sub_lists[(size_t)7 * h->n_channels + sub_count[7]++] = c;
-        }
-      }
+      // only the modes are read under the lock
+      lists.assign((size_t)kRxLists * h->n_channels, 0u);
+      rx_build_lists(h->h_cfg.data(), h->n_channels, true, subset->data(), (uint32_t)subset->size(), lists.data(), sub_count);
     }
   }
-  if (opt.subset != nullptr && !opt.subset->empty())
+  if (subset != nullptr && !subset->empty())
   {
     // (outside the configuration lock: the CLI thread's setters do not wait for this upload)
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(h->d_sub_lists, sub_lists.data(), sizeof(uint32_t) * sub_lists.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    HIP_TRY(hipMemcpy(h->d_sub_lists, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice));
   }
-  const uint32_t *const list_count = (opt.subset != nullptr) ? sub_count : h->list_count;
-  const uint32_t *const d_lists = (opt.subset != nullptr) ? h->d_sub_lists : h->d_lists;
-  if (opt.subset != nullptr && opt.subset->empty())
-  {
-    return HRFD_OK;
-  }
-  int rc = apply_resets(h, s, resets);
-  if (rc != HRFD_OK)
-  {
-    return rc;
-  }
+  return HRFD_OK;
+}
 
-  // launch-local scratch (present flags, cross-block check values) and the
-  // magnitude buffer used when the caller does not want one
-  const size_t units = (size_t)h->n_channels * n_blocks;
-  const size_t ounits = (size_t)h->n_channels * opt.out_blocks;
-  if (std::max(units, ounits) > h->cap_units)
+// launch-local scratch (present flags, cross-block check values), the magnitude buffer used when the caller does not
+// want one, and the SSB channels' 8 kS/s rails
+static int rx_grow_scratch(hrfd_rx *h, const RxCall &c, uint32_t n256, bool has_ssb)
+{
+  const size_t units = (size_t)h->n_channels * c.n_blocks;
+  const size_t need = std::max(units, (size_t)h->n_channels * c.opt.out_blocks);
+  if (need > h->unit_cap())
   {
-    HIP_TRY(hipStreamSynchronize(s));
-    const size_t need = std::max(units, ounits);
-    size_t c1 = 0, c2 = 0, c3 = 0, c4 = 0;
-    h->cap_units = 0;
-    if ((rc = grow((void **)&h->d_present, &c1, need)) != HRFD_OK) return rc;
-    if ((rc = grow((void **)&h->d_magnitude, &c2, need * 4)) != HRFD_OK) return rc;
-    if ((rc = grow((void **)&h->d_chk_pub, &c3, need * 4)) != HRFD_OK) return rc;
-    if ((rc = grow((void **)&h->d_chk_spec, &c4, need * 4)) != HRFD_OK) return rc;
-    h->cap_units = need;
+    HIP_TRY(hipStreamSynchronize(c.s));
+    int rc;
+    if ((rc = h->d_present.grow_bytes(need)) != HRFD_OK) return rc;
+    if ((rc = h->d_magnitude.grow_bytes(need * 4)) != HRFD_OK) return rc;
+    if ((rc = h->d_chk_pub.grow_bytes(need * 4)) != HRFD_OK) return rc;
+    if ((rc = h->d_chk_spec.grow_bytes(need * 4)) != HRFD_OK) return rc;
   }
+  const size_t ssb = units * (size_t)(n256 / 32) * 2 * sizeof(int16_t);
+  if (has_ssb && ssb > h->d_ssb_iq.cap)
+  {
+    HIP_TRY(hipStreamSynchronize(c.s));
+    return h->d_ssb_iq.grow_bytes(ssb);
+  }
+  return HRFD_OK;
+}
 
-  if (list_count[HRFD_MODE_LSB] + list_count[HRFD_MODE_USB] != 0)
-  {
-    const size_t need = units * (size_t)(n256 / 32) * 2 * sizeof(int16_t);
-    if (need > h->cap_ssb)
-    {
-      HIP_TRY(hipStreamSynchronize(s));
-      if ((rc = grow((void **)&h->d_ssb_iq, &h->cap_ssb, need)) != HRFD_OK) return rc;
-    }
-  }
+// what every kernel of the launch is given; a step of the plan sets its own list, runs and flags on a copy (rx_execute)
+static void rx_fill_params(hrfd_rx *h, const RxCall &c, const RxGeometry &g, RxParams &P)
+{
   // per-launch counters: two sets used alternately, each cleared by the previous launch's k_rx_commit
   h->parity ^= 1;
-  uint32_t *const local = h->parity ? h->d_counters + kNumDevCounters : h->d_counters;
-  uint32_t *const other = h->parity ? h->d_counters : h->d_counters + kNumDevCounters;
+  uint32_t *const local = h->parity ? h->d_counters + kNumDevCounters : h->d_counters.p;
+  uint32_t *const other = h->parity ? h->d_counters.p : h->d_counters + kNumDevCounters;
   h->d_local = local;
 
-  RxParams P;
   memset(&P, 0, sizeof(P));
-  P.iq = d_iq;
-  P.ch_stride = channel_stride;
-  P.block_bytes = block_bytes;
-  P.n_blocks = n_blocks;
-  P.n256 = n256;
-  P.ntiles = ntiles;
-  P.origin = origin;
-  P.hal = hal;
-  P.warm_tiles = warm_tiles;
-  P.seed_terms = seed_terms;
+  P.iq = c.d_iq;
+  P.ch_stride = c.channel_stride;
+  P.block_bytes = c.block_bytes;
+  P.n_blocks = c.n_blocks;
+  P.n256 = g.n256;
+  P.ntiles = g.ntiles;
+  P.origin = g.origin;
+  P.hal = g.hal;
+  P.warm_tiles = g.warm_tiles;
+  P.seed_terms = g.seed_terms;
   P.seed_ct = (float)pow(-(double)DEEMPH_A1, (double)kTile);
-  P.serial = opt.serial;
-  P.src256 = opt.src256;
+  P.serial = c.opt.serial;
+  P.src256 = c.opt.src256;
   P.stagger = h->stagger & 63;
   P.run_len = 1;
-  P.n_runs = n_blocks;
+  P.n_runs = c.n_blocks;
   P.dbg_flags = h->stagger >> 8;
-  P.out_blocks = opt.out_blocks;
-  P.out_b0 = opt.out_b0;
-  P.gain_db = gain_db;
+  P.out_blocks = c.opt.out_blocks;
+  P.out_b0 = c.opt.out_b0;
+  P.gain_db = c.gain_db;
   P.state = h->d_state;
   P.state_out = h->d_state_out;
   P.cfg = h->d_cfg;
-  P.pcm = d_pcm;
-  P.magnitude = (d_magnitude != nullptr) ? d_magnitude : h->d_magnitude;
+  P.pcm = c.d_pcm;
+  P.magnitude = (c.d_magnitude != nullptr) ? c.d_magnitude : h->d_magnitude.p;
   P.present = h->d_present;
-  P.iq256 = d_iq256;
+  P.iq256 = c.d_iq256;
   P.ssb_iq = h->d_ssb_iq;
   P.atan2_lut = h->d_lut;
   P.at_corr = h->d_atcorr;
@@ -854,23 +692,23 @@ static int rx_launch(hrfd_rx *h, const int8_t *d_iq, uint64_t channel_stride, ui
   EpilogueParams E;
   memset(&E, 0, sizeof(E));
   E.n_channels = h->n_channels;
-  E.n_blocks = n_blocks;
-  E.n_pcm_per_block = n256 / 32;
-  E.out_blocks = opt.out_blocks;
-  E.out_b0 = opt.out_b0;
+  E.n_blocks = c.n_blocks;
+  E.n_pcm_per_block = g.n256 / 32;
+  E.out_blocks = c.opt.out_blocks;
+  E.out_b0 = c.opt.out_b0;
   E.cfg = h->d_cfg;
   E.state = h->d_state;
   E.state_out = h->d_state_out;
   E.present = h->d_present;
-  E.allowed = d_allowed;
-  E.n_pcm = d_n_pcm;
+  E.allowed = c.d_allowed;
+  E.n_pcm = c.d_n_pcm;
   E.chk_pub = h->d_chk_pub;
   E.chk_spec = h->d_chk_spec;
   E.counters = local;
   E.sticky = h->d_counters;
   E.next_local = other;
   E.chan_list = nullptr;
-  E.first_channel = (opt.subset != nullptr) ? opt.subset->front() : 0u;
+  E.first_channel = (c.opt.subset != nullptr) ? c.opt.subset->front() : 0u;
   E.chan_fail = h->d_chan;
   E.chan_poison = h->d_chan + h->n_channels;
   E.chan_expired = h->d_chan + 2 * (size_t)h->n_channels;
@@ -878,340 +716,234 @@ static int rx_launch(hrfd_rx *h, const int8_t *d_iq, uint64_t channel_stride, ui
   P.fin = E;
   P.self_finish = 0;
   P.sticky = h->d_counters;
+}
 
-  // (an event record is a packet of its own on the queue, ~3 us each: bracketing EVERY launch of a back-to-back
-  //  sequence puts ~6 us of gap between kernels that otherwise follow each other without any -- measured, 256 x 16:
-  //  0.2237 ms per step with the events, 0.2166 without; hrfd_rx_debug_timing_every samples instead)
-  const size_t ev_slots = (h->ev.size() / 2 != 0 && (h->ev_seen++ % h->ev_every) == 0) ? h->ev.size() / 2 : 0;
-  const size_t ev_slot = ev_slots ? (h->ev_launches % ev_slots) : 0;
-  if (ev_slots)
+// Any block length: k_rx_ragged.  One workgroup per channel, the call's blocks in order, every stage with its commutator
+// position: exact, no speculation, every channel commits.  A length that is not a whole number of PCM samples (512 bytes;
+// inner API 64) takes the handle off the grid for good: its state moves from ChanState to RagState (k_rag_expand, once).
+// E: the launch's bookkeeping (rx_fill_params); sub_list: the subset's channels, or nullptr with n_list = all of them.
+static int launch_ragged(hrfd_rx *h, const RxCall &c, const EpilogueParams &E, const uint32_t *sub_list, uint32_t n_list)
+{
+  const int src256 = c.opt.src256;
+  if ((c.block_bytes % (src256 ? 64u : 512u)) != 0)
+  {
+    h->offgrid = true;
+  }
+  if (h->offgrid && !h->rag_built)
+  {
+    if (h->d_rag == nullptr)
+    {
+      HIP_TRY(hipStreamSynchronize(c.s));
+      if (!h->d_rag.alloc(h->n_channels))
+      {
+        return HRFD_ENOMEM;
+      }
+    }
+    HIP_TRY(hipMemsetAsync(h->d_rag, 0, sizeof(RagState) * h->n_channels, c.s));
+    hipLaunchKernelGGL(k_rag_expand, dim3(h->n_channels), dim3(kRagThreads), 0, c.s, h->d_state.p, h->d_rag.p, h->d_lut.p, h->n_channels);
+    HIP_TRY(hipGetLastError());
+    h->rag_built = true;
+  }
+  RagParams R;
+  memset(&R, 0, sizeof(R));
+  R.iq = c.d_iq;
+  R.ch_stride = c.channel_stride;
+  R.block_bytes = c.block_bytes;
+  R.n_blocks = c.n_blocks;
+  R.src256 = src256;
+  R.offgrid = h->offgrid ? 1 : 0;
+  R.pcm_cap = src256 ? (c.block_bytes + 63u) / 64u : (c.block_bytes + 511u) / 512u;
+  R.iq256_cap = 2u * ((c.block_bytes / 2u + 7u) / 8u);
+  R.out_blocks = c.opt.out_blocks;
+  R.out_b0 = c.opt.out_b0;
+  R.chan_list = sub_list;
+  R.n_list = n_list;
+  R.gain_db = c.gain_db;
+  R.state = h->d_state;
+  R.rag = h->d_rag;
+  R.cfg = h->d_cfg;
+  R.pcm = c.d_pcm;
+  R.n_pcm = c.d_n_pcm;
+  R.magnitude = (c.d_magnitude != nullptr) ? c.d_magnitude : h->d_magnitude.p;
+  R.allowed = c.d_allowed;
+  R.iq256 = c.d_iq256;
+  R.atan2_lut = h->d_lut;
+  R.dbfs = h->d_dbfs;
+  R.counters = E.counters;
+  R.sticky = E.sticky;
+  R.next_local = E.next_local;
+  R.first_channel = E.first_channel;
+  R.chan_fail = E.chan_fail;
+  R.chan_poison = E.chan_poison;
+  hipLaunchKernelGGL(k_rx_ragged, dim3(R.n_list), dim3(kRagThreads), 0, c.s, R);
+  HIP_TRY(hipGetLastError());
+  h->ragged_launches++;
+  return HRFD_OK;
+}
+
+// the plan's input: the lists' sizes, the call, the handle's knobs
+static RxPlanIn rx_plan_input(const hrfd_rx *h, const RxCall &c, const RxGeometry &g, const uint32_t *count)
+{
+  RxPlanIn in;
+  memcpy(in.count, count, sizeof(in.count));
+  in.n_channels = h->n_channels;
+  in.n_blocks = c.n_blocks;
+  in.n256 = g.n256;
+  in.gain_db = c.gain_db;
+  in.max_threshold = h->wbfm_max_threshold;
+  in.warm_tiles = g.warm_tiles;
+  in.serial = c.opt.serial != 0;
+  in.src256 = c.opt.src256 != 0;
+  in.subset = c.opt.subset != nullptr;
+  in.dump = c.d_iq256 != nullptr;
+  in.use_stream = h->use_stream;
+  in.atan_mode = h->atan_mode;
+  in.fir_flow = h->fir_flow;
+  in.gated_pass = h->gated_pass;
+  in.run_len = h->run_len;
+  in.tab_ok = h->tab_ok;
+  in.quad_ok = h->quad_ok;
+  in.arith_ok = h->arith_ok;
+  in.has_dbg = h->d_dbg != nullptr;
+  in.dbg_cap = h->d_dbg.cap / sizeof(unsigned long long);
+  return in;
+}
+
+// the plan's steps, in order, on the caller's stream: each on its own copy of the launch's parameters
+static int rx_execute(hrfd_rx *h, const RxPlan &plan, const RxParams &base, const uint32_t *d_lists, hipStream_t s)
+{
+  for (int i = 0; i < plan.n; i++)
+  {
+    const RxStep &st = plan.step[i];
+    const uint32_t *const list = (st.list >= 0) ? d_lists + (size_t)st.list * h->n_channels : nullptr;
+    const dim3 grid(st.grid), block(st.block);
+    if (st.kernel == kRxFinish)
+    {
+      EpilogueParams G = base.fin;
+      G.chan_list = list;
+      G.n_channels = st.n_list;
+      hipLaunchKernelGGL(k_rx_finish, grid, block, 0, s, G);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
+    RxParams P = base;
+    P.chan_list = list;
+    P.n_list = st.n_list;
+    P.run_len = st.run_len;
+    P.n_runs = st.n_runs;
+    P.warm_tiles = st.warm_tiles;
+    P.self_finish = st.self_finish ? 1 : 0;
+    P.dbg = st.dbg ? h->d_dbg.p : nullptr;
+    if (st.expire_once)
+    {
+      P.dbg_flags |= h->expire_once << 16;
+      h->expire_once = 0;
+    }
+    switch (st.kernel)
+    {
+      case kRxFlowBank: hipLaunchKernelGGL((k_rx_flow_bank<HRFD_FLOW_SVC, false>), grid, block, 0, s, P); break;
+      case kRxFlowBankDump: hipLaunchKernelGGL((k_rx_flow_bank<HRFD_FLOW_SVC, true>), grid, block, 0, s, P); break;
+      case kRxFlowAs: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false, 14>), grid, block, 0, s, P); break;
+      case kRxFlowAsDump: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, true, 14>), grid, block, 0, s, P); break;
+      case kRxFlowFm: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false, 2>), grid, block, 0, s, P); break;
+      case kRxFlowFmDump: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, true, 2>), grid, block, 0, s, P); break;
+      case kRxFlowWb: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false>), grid, block, 0, s, P); break;
+      case kRxFlowWbDump: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, true>), grid, block, 0, s, P); break;
+      case kRxGatedWb: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, true, false>), grid, block, 0, s, P); break;
+      case kRxGatedFm: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, true, false, 2>), grid, block, 0, s, P); break;
+      case kRxGatedAs: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, true, false, 14>), grid, block, 0, s, P); break;
+      case kRxFirAs: hipLaunchKernelGGL((k_rx_fir<14, false, false>), grid, block, 0, s, P); break;
+      case kRxFirAs256: hipLaunchKernelGGL((k_rx_fir<14, true, false>), grid, block, 0, s, P); break;
+      case kRxPostAs: hipLaunchKernelGGL((k_rx_post<14>), grid, block, 0, s, P); break;
+      case kRxFirFm: hipLaunchKernelGGL((k_rx_fir<2, false, false>), grid, block, 0, s, P); break;
+      case kRxFirFm256: hipLaunchKernelGGL((k_rx_fir<2, true, false>), grid, block, 0, s, P); break;
+      case kRxFirFmArith: hipLaunchKernelGGL((k_rx_fir<2, false, true>), grid, block, 0, s, P); break;
+      case kRxBlocksNone: hipLaunchKernelGGL((k_rx_wbfm<0, false, false>), grid, block, 0, s, P); break;
+      case kRxBlocksWb: hipLaunchKernelGGL((k_rx_wbfm<3, false, false>), grid, block, 0, s, P); break;
+      case kRxBlocksWb256: hipLaunchKernelGGL((k_rx_wbfm<3, true, false>), grid, block, 0, s, P); break;
+      case kRxBlocksWbArith: hipLaunchKernelGGL((k_rx_wbfm<3, false, true>), grid, block, 0, s, P); break;
+      default: return fail(HRFD_ESTATE, "internal: no kernel %d", (int)st.kernel);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  return HRFD_OK;
+}
+
+// The measurement hook's bracket around the kernels of a launch: returns the slot whose events take it, or -1.
+// (an event record is a packet of its own on the queue, ~3 us each: bracketing EVERY launch of a back-to-back
+//  sequence puts ~6 us of gap between kernels that otherwise follow each other without any -- measured, 256 x 16:
+//  0.2237 ms per step with the events, 0.2166 without; hrfd_rx_debug_timing_every samples instead)
+static int rx_timing_slot(hrfd_rx *h)
+{
+  const size_t slots = h->ev.size() / 2;
+  return (slots != 0 && (h->ev_seen++ % h->ev_every) == 0) ? (int)(h->ev_launches % slots) : -1;
+}
+
+static int rx_launch(hrfd_rx *h, const int8_t *d_iq, uint64_t channel_stride, uint32_t block_bytes,
+                     uint32_t n_blocks, uint32_t gain_db, int16_t *d_pcm, uint32_t *d_n_pcm,
+                     uint32_t *d_magnitude, uint8_t *d_allowed, int8_t *d_iq256, hipStream_t s,
+                     const LaunchOpts &opt)
+{
+  if (h == nullptr || d_iq == nullptr || d_pcm == nullptr)
+  {
+    return fail(HRFD_EINVAL, "hrfd_rx_process: NULL handle or buffer");
+  }
+  const RxCall call = {d_iq, channel_stride, block_bytes, n_blocks, gain_db, d_pcm, d_n_pcm, d_magnitude, d_allowed, d_iq256, s, opt};
+  int rc;
+  // 1. geometry
+  RxGeometry g;
+  if ((rc = rx_geometry(block_bytes, n_blocks, channel_stride, opt.out_b0, opt.out_blocks, opt.serial, opt.src256, h->offgrid,
+                        h->warm, &g)) != HRFD_OK)
+  {
+    return rc;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  // 2. configuration snapshot
+  const bool subset = opt.subset != nullptr;
+  uint32_t sub_count[kRxLists] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<std::pair<uint32_t, int>> resets;
+  if ((rc = rx_snapshot(h, call, sub_count, resets)) != HRFD_OK)
+  {
+    return rc;
+  }
+  if (subset && opt.subset->empty())
+  {
+    return HRFD_OK;
+  }
+  const uint32_t *const list_count = subset ? sub_count : h->list_count;
+  const uint32_t *const d_lists = subset ? h->d_sub_lists.p : h->d_lists.p;
+  if ((rc = apply_resets(h, s, resets)) != HRFD_OK)
+  {
+    return rc;
+  }
+  // 3. scratch
+  if ((rc = rx_grow_scratch(h, call, g.n256, list_count[HRFD_MODE_LSB] + list_count[HRFD_MODE_USB] != 0)) != HRFD_OK)
+  {
+    return rc;
+  }
+  // 4. parameters
+  RxParams P;
+  rx_fill_params(h, call, g, P);
+  const int ev_slot = rx_timing_slot(h);
+  if (ev_slot >= 0)
   {
     HIP_TRY(hipEventRecord(h->ev[2 * ev_slot], s));
   }
-  if (ragged)
+  if (g.ragged)
   {
-    // ---------------------------------------------------------------- any block length: k_rx_ragged
-    // One workgroup per channel, the call's blocks in order, every stage with its commutator position: exact, no
-    // speculation, every channel commits.  A length that is not a whole number of PCM samples (512 bytes; inner API
-    // 64) takes the handle off the grid for good: its state moves from ChanState to RagState (k_rag_expand, once).
-    if ((block_bytes % (opt.src256 ? 64u : 512u)) != 0)
-    {
-      h->offgrid = true;
-    }
-    if (h->offgrid && !h->rag_built)
-    {
-      if (h->d_rag == nullptr)
-      {
-        HIP_TRY(hipStreamSynchronize(s));
-        hipError_t e = hipMalloc((void **)&h->d_rag, sizeof(RagState) * h->n_channels);
-        if (e != hipSuccess)
-        {
-          h->d_rag = nullptr;
-          return fail(HRFD_ENOMEM, "hipMalloc(%zu) failed: %s", sizeof(RagState) * h->n_channels, hipGetErrorString(e));
-        }
-      }
-      HIP_TRY(hipMemsetAsync(h->d_rag, 0, sizeof(RagState) * h->n_channels, s));
-      hipLaunchKernelGGL(k_rag_expand, dim3(h->n_channels), dim3(kRagThreads), 0, s, h->d_state, h->d_rag, h->d_lut, h->n_channels);
-      HIP_TRY(hipGetLastError());
-      h->rag_built = true;
-    }
-    RagParams R;
-    memset(&R, 0, sizeof(R));
-    R.iq = d_iq;
-    R.ch_stride = channel_stride;
-    R.block_bytes = block_bytes;
-    R.n_blocks = n_blocks;
-    R.src256 = opt.src256;
-    R.offgrid = h->offgrid ? 1 : 0;
-    R.pcm_cap = opt.src256 ? (block_bytes + 63u) / 64u : (block_bytes + 511u) / 512u;
-    R.iq256_cap = 2u * ((block_bytes / 2u + 7u) / 8u);
-    R.out_blocks = opt.out_blocks;
-    R.out_b0 = opt.out_b0;
-    R.chan_list = (opt.subset != nullptr) ? d_lists + (size_t)6 * h->n_channels : nullptr;
-    R.n_list = (opt.subset != nullptr) ? list_count[6] : h->n_channels;
-    R.gain_db = gain_db;
-    R.state = h->d_state;
-    R.rag = h->d_rag;
-    R.cfg = h->d_cfg;
-    R.pcm = d_pcm;
-    R.n_pcm = d_n_pcm;
-    R.magnitude = (d_magnitude != nullptr) ? d_magnitude : h->d_magnitude;
-    R.allowed = d_allowed;
-    R.iq256 = d_iq256;
-    R.atan2_lut = h->d_lut;
-    R.dbfs = h->d_dbfs;
-    R.counters = local;
-    R.sticky = h->d_counters;
-    R.next_local = other;
-    R.first_channel = E.first_channel;
-    R.chan_fail = E.chan_fail;
-    R.chan_poison = E.chan_poison;
-    hipLaunchKernelGGL(k_rx_ragged, dim3(R.n_list), dim3(kRagThreads), 0, s, R);
-    HIP_TRY(hipGetLastError());
-    h->ragged_launches++;
-    if (ev_slots)
-    {
-      HIP_TRY(hipEventRecord(h->ev[2 * ev_slot + 1], s));
-      h->ev_launches++;
-    }
-    h->last_stream = s;
-    return HRFD_OK;
-  }
-  // ---------------------------------------------------------------- dispatch
-  // Everything goes to the caller's stream, in this order of preference:
-  //  1. k_rx_flow_bank: a bank of several kinds (WBFM, FM, AM / SSB) as ONE launch -- one persistent workgroup per
-  //     channel, the mode read per workgroup, every channel finished inside (BASELINE config 3);
-  //  2. k_rx_wbfm_flow<.., MODE> per kind, the same shape, when there are channels enough of that kind to fill the
-  //     chip that way (WBFM: always; BASELINE configs 2 and 4), behind it the gated pass for WBFM channels whose
-  //     squelch gates may close;
-  //  3. the block kernels (one workgroup per channel-block: k_rx_wbfm, k_rx_fir + k_rx_post) with k_rx_finish behind
-  //     them: single-block calls (the reference's cadence), the inner demodulator API, the exact replay of a subset,
-  //     block sizes that are not whole units of 512 samples at 256 kS/s, small banks.
-  // The flow shapes need whole units of two 4 KiB pieces per block, at most 64 blocks, and the first-octant table.
-  P.dbg = nullptr;
-  const uint32_t n_wb = list_count[HRFD_MODE_WBFM], n_as = list_count[7], n_fm = list_count[HRFD_MODE_FM];
-  const bool batch = n_blocks > 1 && !opt.serial && !opt.src256 && opt.subset == nullptr;
-  // (the flow shapes need their tables: the first-octant one with its corrections -- FM, and the round-4 WBFM build --
-  //  and the first-quadrant one of the re-split WBFM chain; both are proven against the reference table at create)
-  const bool flow_shape = batch && h->use_stream == 2 && h->tab_ok && (HRFD_FLOW_SPLIT == 0 || h->quad_ok) && h->atan_mode != 0 &&
-                          (n256 % 512u) == 0 && n256 >= 2048u;
-  const bool flow = flow_shape && n_wb != 0;              // the WBFM channels run on the flow kernel
-  const bool fir_shape = flow_shape && h->fir_flow != 0 && n_blocks <= 64u;
-  const int kinds = (n_wb != 0) + (n_as != 0) + (n_fm != 0);
-  const bool bank = fir_shape && kinds >= 2 && h->fir_flow != 2 && (h->fir_flow > 0 || list_count[9] >= 48u);
-  const bool as_flow = !bank && fir_shape && n_as != 0 && (h->fir_flow > 0 || n_as >= 48u);
-  const bool fm_flow = !bank && fir_shape && n_fm != 0 && (h->fir_flow > 0 || n_fm >= 48u);
-  const bool may_close = (int64_t)h->wbfm_max_threshold > -42 - (int64_t)gain_db;   // can a WBFM gate close at all? (see below)
-
-  // k_rx_wbfm_flow / k_rx_flow_bank over a channel list: one run per channel unless the WBFM bank alone is too small
-  // to fill the chip with whole-CU workgroups
-  auto launch_flow = [&](int list, uint32_t n, int mode) -> int {
-    P.chan_list = d_lists + (size_t)list * h->n_channels;
-    P.n_list = n;
-    const uint32_t groups = 8u * ((n + 7u) / 8u);
-    uint32_t run_len = n_blocks;
-    if (mode == HRFD_MODE_WBFM)
-    {
-      // runs of consecutive blocks per workgroup (only a run's first block re-produces the history in front of it):
-      // as long as possible while the launch still fills the chip -- up to the 64 blocks a workgroup can finish from LDS
-      // (round 5; rounds 2-4 stopped at 16: a 64-block batch of 256 channels was four runs per channel, each with its own
-      // table copy, re-derived history and service tail -- `also.wbfm_256x64` of the bench line)
-      run_len = (h->run_len > 0) ? (uint32_t)h->run_len : 64u;
-      run_len = std::min(run_len, n_blocks);
-      while (h->run_len <= 0 && run_len > 1 && groups * ((n_blocks + run_len - 1) / run_len) < 256u)
-      {
-        run_len--;
-      }
-    }
-    P.run_len = run_len;
-    P.n_runs = (n_blocks + run_len - 1) / run_len;
-    const uint32_t grid = groups * P.n_runs;
-    P.dbg = (h->d_dbg != nullptr && (size_t)grid * kDbgSlots <= h->dbg_cap) ? h->d_dbg : nullptr;   // (probe builds: one launch per call -- one mode, or the bank)
-    P.warm_tiles = std::min(warm_tiles, HRFD_FLOW_WARM_TILES);   // tiles of 64 here (the FIR modes: ring tiles read below a generation)
-    P.self_finish = 1;                                     // the last workgroup of a channel finishes it (finish_channel)
-    P.dbg_flags |= h->expire_once << 16;
-    h->expire_once = 0;
-    const bool dump = d_iq256 != nullptr;                   // (`enable iqdump`: the 256 kS/s stream goes out of the stream waves as well)
-    if (mode < 0)
-    {
-      if (dump) hipLaunchKernelGGL((k_rx_flow_bank<HRFD_FLOW_SVC, true>), dim3(grid), dim3(kThreads), 0, s, P);
-      else hipLaunchKernelGGL((k_rx_flow_bank<HRFD_FLOW_SVC, false>), dim3(grid), dim3(kThreads), 0, s, P);
-    }
-    else if (mode == HRFD_MODE_FM)
-    {
-      if (dump) hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, true, 2>), dim3(grid), dim3(kThreads), 0, s, P);
-      else hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false, 2>), dim3(grid), dim3(kThreads), 0, s, P);
-    }
-    else if (mode != HRFD_MODE_WBFM)
-    {
-      if (dump) hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, true, 14>), dim3(grid), dim3(kThreads), 0, s, P);
-      else hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false, 14>), dim3(grid), dim3(kThreads), 0, s, P);
-    }
-    else if (d_iq256 != nullptr)
-    {
-      hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, true>), dim3(grid), dim3(kThreads), 0, s, P);
-    }
-    else
-    {
-      hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false>), dim3(grid), dim3(kThreads), 0, s, P);
-    }
-    P.dbg_flags &= 0xffff;
-    P.dbg = nullptr;
-    HIP_TRY(hipGetLastError());
-    // Squelch (Squelch.cc:227-273, IqDataProcessor.cc:961-1034).  The detector's lowest level is 0 - 42 - gain_db dBFS
-    // (DbfsCalculator.cc:111-147): with a threshold at or below it -- the reference's default is -200 -- no gate of
-    // the bank can ever close and the batch launch is all there is.  Otherwise the gated pass follows, one launch per
-    // kind: its workgroups redo the channels that failed on a closed gate, exactly, and the others leave at once.
-    if (h->gated_pass && n_blocks <= 64u && may_close)
-    {
-      P.run_len = n_blocks;
-      P.n_runs = 1;
-      auto gated = [&](int glist, uint32_t gn, int gmode) {
-        if (gn == 0)
-        {
-          return;
-        }
-        P.chan_list = d_lists + (size_t)glist * h->n_channels;
-        P.n_list = gn;
-        const dim3 gg(8u * ((gn + 7u) / 8u));
-        if (gmode == HRFD_MODE_WBFM)
-        {
-          hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, true, false>), gg, dim3(kThreads), 0, s, P);
-        }
-        else if (gmode == HRFD_MODE_FM)
-        {
-          hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, true, false, 2>), gg, dim3(kThreads), 0, s, P);
-        }
-        else
-        {
-          hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, true, false, 14>), gg, dim3(kThreads), 0, s, P);
-        }
-      };
-      if (mode < 0 || mode == HRFD_MODE_WBFM) gated(HRFD_MODE_WBFM, n_wb, HRFD_MODE_WBFM);
-      if (mode < 0 || mode == HRFD_MODE_FM) gated(HRFD_MODE_FM, n_fm, HRFD_MODE_FM);
-      if (mode < 0 || (mode != HRFD_MODE_WBFM && mode != HRFD_MODE_FM && mode >= 0)) gated(7, n_as, HRFD_MODE_AM);
-      HIP_TRY(hipGetLastError());
-    }
-    P.self_finish = 0;
-    P.warm_tiles = warm_tiles;
-    return HRFD_OK;
-  };
-  // the block kernels of mode NONE (front end and squelch only) and WBFM: runs of blocks per workgroup
-  auto launch_wbfm_blocks = [&](int m) -> int {
-    const uint32_t n = list_count[m];
-    P.chan_list = d_lists + (size_t)m * h->n_channels;
-    P.n_list = n;
-    const uint32_t groups = 8u * ((n + 7u) / 8u);
-    uint32_t run_len = (h->run_len > 0) ? (uint32_t)h->run_len : 8u;
-    run_len = std::min(run_len, n_blocks);
-    while (h->run_len <= 0 && run_len > 1 && groups * ((n_blocks + run_len - 1) / run_len) < 512u)
-    {
-      run_len--;
-    }
-    if (opt.serial || opt.src256)
-    {
-      run_len = 1;
-    }
-    P.run_len = run_len;
-    P.n_runs = (n_blocks + run_len - 1) / run_len;
-    const uint32_t grid = groups * P.n_runs;
-    P.dbg = (h->d_dbg != nullptr && (size_t)grid * kDbgSlots <= h->dbg_cap && m == HRFD_MODE_WBFM) ? h->d_dbg : nullptr;
-    if (m == HRFD_MODE_NONE)
-    {
-      hipLaunchKernelGGL((k_rx_wbfm<0, false, false>), dim3(grid), dim3(kThreads), 0, s, P);
-    }
-    else if (opt.src256)
-    {
-      hipLaunchKernelGGL((k_rx_wbfm<3, true, false>), dim3(grid), dim3(kThreads), 0, s, P);
-    }
-    else if (h->arith_ok && h->atan_mode != 0)
-    {
-      hipLaunchKernelGGL((k_rx_wbfm<3, false, true>), dim3(grid), dim3(kThreads), 0, s, P);
-    }
-    else
-    {
-      hipLaunchKernelGGL((k_rx_wbfm<3, false, false>), dim3(grid), dim3(kThreads), 0, s, P);
-    }
-    P.dbg = nullptr;
-    HIP_TRY(hipGetLastError());
-    return HRFD_OK;
-  };
-
-  if (bank)
-  {
-    if ((rc = launch_flow(9, list_count[9], -1)) != HRFD_OK) return rc;
+    rc = launch_ragged(h, call, P.fin, subset ? d_lists + (size_t)kRxListNotWb * h->n_channels : nullptr,
+                       subset ? list_count[kRxListNotWb] : h->n_channels);
   }
   else
   {
-    // AM and SSB: one launch for both kinds (the same three decimators), then their 8 kS/s recurrences
-    if (as_flow)
-    {
-      if ((rc = launch_flow(7, n_as, HRFD_MODE_AM)) != HRFD_OK) return rc;
-    }
-    else if (n_as != 0)
-    {
-      P.chan_list = d_lists + (size_t)7 * h->n_channels;
-      P.n_list = n_as;
-      const uint32_t grid = 8u * ((n_as + 7u) / 8u) * n_blocks;
-      if (opt.src256)
-      {
-        hipLaunchKernelGGL((k_rx_fir<14, true, false>), dim3(grid), dim3(kThreads), 0, s, P);
-      }
-      else
-      {
-        hipLaunchKernelGGL((k_rx_fir<14, false, false>), dim3(grid), dim3(kThreads), 0, s, P);
-      }
-      hipLaunchKernelGGL(k_rx_post<14>, dim3(n_as), dim3(256), 0, s, P);
-      HIP_TRY(hipGetLastError());
-    }
-    if (fm_flow)
-    {
-      if ((rc = launch_flow(HRFD_MODE_FM, n_fm, HRFD_MODE_FM)) != HRFD_OK) return rc;
-    }
-    else if (n_fm != 0)
-    {
-      P.chan_list = d_lists + (size_t)HRFD_MODE_FM * h->n_channels;
-      P.n_list = n_fm;
-      const uint32_t grid = 8u * ((n_fm + 7u) / 8u) * n_blocks;
-      if (opt.src256)
-      {
-        hipLaunchKernelGGL((k_rx_fir<2, true, false>), dim3(grid), dim3(kThreads), 0, s, P);
-      }
-      else if (h->arith_ok && h->atan_mode != 0)
-      {
-        hipLaunchKernelGGL((k_rx_fir<2, false, true>), dim3(grid), dim3(kThreads), 0, s, P);
-      }
-      else
-      {
-        hipLaunchKernelGGL((k_rx_fir<2, false, false>), dim3(grid), dim3(kThreads), 0, s, P);
-      }
-      HIP_TRY(hipGetLastError());
-    }
-    if (flow)
-    {
-      if ((rc = launch_flow(HRFD_MODE_WBFM, n_wb, HRFD_MODE_WBFM)) != HRFD_OK) return rc;
-    }
-    else if (n_wb != 0)
-    {
-      if ((rc = launch_wbfm_blocks(HRFD_MODE_WBFM)) != HRFD_OK) return rc;
-    }
+    // 5. plan, 6. execute
+    rc = rx_execute(h, rx_plan(rx_plan_input(h, call, g, list_count)), P, d_lists, s);
   }
-  if (list_count[HRFD_MODE_NONE] != 0)
+  if (rc != HRFD_OK)
   {
-    if ((rc = launch_wbfm_blocks(HRFD_MODE_NONE)) != HRFD_OK) return rc;
+    return rc;
   }
-  // the channels that no kernel finished by itself
-  auto finish_list = [&](const uint32_t *list, uint32_t n) -> int {
-    if (n != 0)
-    {
-      EpilogueParams G = E;
-      G.chan_list = list;
-      G.n_channels = n;
-      hipLaunchKernelGGL(k_rx_finish, dim3(n), dim3(64), 0, s, G);
-      HIP_TRY(hipGetLastError());
-    }
-    return HRFD_OK;
-  };
-  if (opt.subset != nullptr)
-  {
-    if ((rc = finish_list(d_lists + (size_t)6 * h->n_channels, list_count[6])) != HRFD_OK) return rc;   // the subset itself
-  }
-  else if (!bank && !flow && !as_flow && !fm_flow)
-  {
-    if ((rc = finish_list(nullptr, h->n_channels)) != HRFD_OK) return rc;                                  // everything, one launch
-  }
-  else
-  {
-    for (int m : {HRFD_MODE_NONE, HRFD_MODE_AM, HRFD_MODE_FM, HRFD_MODE_WBFM, HRFD_MODE_LSB, HRFD_MODE_USB})
-    {
-      const bool self = (m == HRFD_MODE_NONE) ? false : bank || (m == HRFD_MODE_WBFM ? flow : m == HRFD_MODE_FM ? fm_flow : as_flow);
-      if (!self)
-      {
-        if ((rc = finish_list(d_lists + (size_t)m * h->n_channels, list_count[m])) != HRFD_OK) return rc;
-      }
-    }
-  }
-  if (ev_slots)
+  if (ev_slot >= 0)
   {
     HIP_TRY(hipEventRecord(h->ev[2 * ev_slot + 1], s));
     h->ev_launches++;
@@ -1460,15 +1192,15 @@ extern "C" int hrfd_rx_process_block(hrfd_rx *h, const int8_t *iq, uint32_t bloc
   hipStream_t s = h->stream;
   int rc;
   HIP_TRY(hipStreamSynchronize(s));
-  if ((rc = grow((void **)&h->d_iq, &h->cap_iq, iq_bytes)) != HRFD_OK) return rc;
-  if ((rc = grow((void **)&h->d_pcm, &h->cap_pcm, pcm_bytes)) != HRFD_OK) return rc;
+  if ((rc = h->d_iq.grow_bytes(iq_bytes)) != HRFD_OK) return rc;
+  if ((rc = h->d_pcm.grow_bytes(pcm_bytes)) != HRFD_OK) return rc;
   if (iq256k_opt != nullptr)
   {
-    if ((rc = grow((void **)&h->d_iq256, &h->cap_iq256, iq256_bytes)) != HRFD_OK) return rc;
+    if ((rc = h->d_iq256.grow_bytes(iq256_bytes)) != HRFD_OK) return rc;
   }
-  if ((rc = grow((void **)&h->d_npcm, &h->cap_npcm, units * 4)) != HRFD_OK) return rc;
-  if ((rc = grow((void **)&h->d_allowed, &h->cap_allowed, units)) != HRFD_OK) return rc;
-  if ((rc = grow((void **)&h->d_mag_out, &h->cap_mag_out, units * 4)) != HRFD_OK) return rc;
+  if ((rc = h->d_npcm.grow_bytes(units * 4)) != HRFD_OK) return rc;
+  if ((rc = h->d_allowed.grow_bytes(units)) != HRFD_OK) return rc;
+  if ((rc = h->d_mag_out.grow_bytes(units * 4)) != HRFD_OK) return rc;
   HIP_TRY(hipMemcpyAsync(h->d_iq, iq, iq_bytes, hipMemcpyHostToDevice, s));
   // mode NONE / squelched units produce no PCM: hand back zeros rather than stale bytes
   HIP_TRY(hipMemsetAsync(h->d_pcm, 0, pcm_bytes, s));
@@ -1671,9 +1403,9 @@ extern "C" int hrfd_demod_process(hrfd_demod *dh, const int8_t *iq256k, uint32_t
   hipStream_t s = h->stream;
   int rc;
   HIP_TRY(hipStreamSynchronize(s));
-  if ((rc = grow((void **)&h->d_iq, &h->cap_iq, iq_bytes)) != HRFD_OK) return rc;
-  if ((rc = grow((void **)&h->d_pcm, &h->cap_pcm, pcm_bytes)) != HRFD_OK) return rc;
-  if ((rc = grow((void **)&h->d_npcm, &h->cap_npcm, (size_t)C * 4)) != HRFD_OK) return rc;
+  if ((rc = h->d_iq.grow_bytes(iq_bytes)) != HRFD_OK) return rc;
+  if ((rc = h->d_pcm.grow_bytes(pcm_bytes)) != HRFD_OK) return rc;
+  if ((rc = h->d_npcm.grow_bytes((size_t)C * 4)) != HRFD_OK) return rc;
   HIP_TRY(hipMemsetAsync(h->d_pcm, 0, pcm_bytes, s));
   HIP_TRY(hipMemcpyAsync(h->d_iq, iq256k, iq_bytes, hipMemcpyHostToDevice, s));
   const LaunchOpts opt = {1, 0, 0, 1};

@@ -67,7 +67,7 @@ extern "C" int hrfd_rx_debug_atan_eval_quad(hrfd_rx *h, float *out65536)
   HIP_TRY(hipSetDevice(h->device));
   float *d = nullptr;
   HIP_TRY(hipMalloc((void **)&d, sizeof(float) * 65536));
-  hipLaunchKernelGGL(k_atan_eval_quad, dim3(256), dim3(256), 0, 0, h->d_atquad, d);
+  hipLaunchKernelGGL(k_atan_eval_quad, dim3(256), dim3(256), 0, 0, h->d_atquad.p, d);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpy(out65536, d, sizeof(float) * 65536, hipMemcpyDeviceToHost);
   (void)hipFree(d);
@@ -92,11 +92,11 @@ static int atan_eval(hrfd_rx *h, float *out65536, bool tab)
   HIP_TRY(hipMalloc((void **)&d, sizeof(float) * 65536));
   if (tab)
   {
-    hipLaunchKernelGGL(k_atan_eval<true>, dim3(256), dim3(256), 0, 0, h->d_atcorr2, h->d_att0, d);
+    hipLaunchKernelGGL(k_atan_eval<true>, dim3(256), dim3(256), 0, 0, h->d_atcorr2.p, h->d_att0.p, d);
   }
   else
   {
-    hipLaunchKernelGGL(k_atan_eval<false>, dim3(256), dim3(256), 0, 0, h->d_atcorr, h->d_atinv, d);
+    hipLaunchKernelGGL(k_atan_eval<false>, dim3(256), dim3(256), 0, 0, h->d_atcorr.p, h->d_atinv.p, d);
   }
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpy(out65536, d, sizeof(float) * 65536, hipMemcpyDeviceToHost);
@@ -289,20 +289,16 @@ extern "C" int hrfd_rx_debug_stamps(hrfd_rx *h, uint32_t cap_groups, unsigned lo
   HIP_TRY(hipSetDevice(h->device));
   if (host_out != nullptr && h->d_dbg != nullptr)
   {
-    HIP_TRY(hipMemcpy(host_out, h->d_dbg, h->dbg_cap * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_out, h->d_dbg, h->d_dbg.cap, hipMemcpyDeviceToHost));
     return HRFD_OK;
   }
-  if (h->d_dbg)
-  {
-    (void)hipFree(h->d_dbg);
-    h->d_dbg = nullptr;
-    h->dbg_cap = 0;
-  }
+  h->d_dbg.release();
   if (cap_groups > 0)
   {
-    HIP_TRY(hipMalloc((void **)&h->d_dbg, (size_t)cap_groups * kDbgSlots * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(h->d_dbg, 0, (size_t)cap_groups * kDbgSlots * sizeof(unsigned long long)));
-    h->dbg_cap = (size_t)cap_groups * kDbgSlots;
+    const size_t bytes = (size_t)cap_groups * kDbgSlots * sizeof(unsigned long long);
+    const int rc = h->d_dbg.grow_bytes(bytes);
+    if (rc != HRFD_OK) return rc;
+    HIP_TRY(hipMemset(h->d_dbg, 0, bytes));
   }
   return HRFD_OK;
 }
@@ -400,7 +396,7 @@ extern "C" int hrfd_rx_debug_set_stagger(hrfd_rx *h, int units)
 // diagnostic hook: the cross-block check values of the latest launch ([n_channels][n_blocks] each)
 extern "C" int hrfd_rx_debug_chk(hrfd_rx *h, float *pub, float *spec, uint32_t n)
 {
-  if (h == nullptr || pub == nullptr || spec == nullptr || n > h->cap_units)
+  if (h == nullptr || pub == nullptr || spec == nullptr || n > h->unit_cap())
   {
     return fail(HRFD_EINVAL, "hrfd_rx_debug_chk: bad arguments");
   }

@@ -1,6 +1,7 @@
 // hackrfdiags_amd/csrc/hrfd_api_tx.hip -- the transmit side of the C ABI (include/hrfd.h): hrfd_mod_* (the four modulators,
 // interpolateSignal and the signals/ generators over k_mod and its baseband passes) and hrfd_nco_*.  Part of the unity
-// translation unit hrfd_lib.hip, behind hrfd_api.hip (errors, HIP_TRY, grow).
+// translation unit hrfd_lib.hip, behind hrfd_api.hip (errors, HIP_TRY) and hrfd_buf.h (DevBuf: the handles own their
+// device buffers).
 // ------------------------------------------------------------------ transmit
 #ifndef HRFD_WB_FUSED
 #define HRFD_WB_FUSED 1                 // round 6: the WBFM modulator's lookup pass and x8 cascade as ONE kernel (k_wb_tail)
@@ -12,26 +13,24 @@ struct hrfd_mod
   uint32_t n_channels = 0;
   hipStream_t stream = nullptr;
   hipStream_t last_stream = nullptr;
-  int16_t *d_tail[2] = {nullptr, nullptr};   // ping-pong: [C][4][kModTail]
+  DevBuf<int16_t> d_tail[2];                 // ping-pong: [C][4][kModTail]
   int cur = 0;
-  uint8_t *d_lsb = nullptr;
+  DevBuf<uint8_t> d_lsb;
   std::vector<uint8_t> h_lsb;
   bool lsb_dirty = true;
   std::mutex mu;
   std::vector<uint32_t> resets;
   // AM / FM: per-channel parameter (modulation index / deviation), FM phase accumulators, and
   // the baseband rails of a call
-  float *d_param = nullptr, *d_acc = nullptr, *d_phase = nullptr;
-  int16_t *d_rails = nullptr;
-  size_t cap_phase = 0, cap_rails = 0;
+  DevBuf<float> d_param, d_acc, d_phase;
+  DevBuf<int16_t> d_rails;
   std::vector<float> h_param;
   bool param_dirty = true;
   // WBFM: the PCM at 256 kS/s, the step/phase/rails cells, Nco::runFast tables, rail history
-  uint32_t *d_wb = nullptr, *d_wbtail[2] = {nullptr, nullptr};
-  size_t cap_wb = 0;
-  float *d_sin = nullptr, *d_cos = nullptr;
-  uint32_t *d_wbpack = nullptr;         // the two tables x900 as int16 rail pairs (k_wb_rails)
-  uint32_t *d_err = nullptr;            // k_phase_scan: waits that expired (never, unless the kernel is broken)
+  DevBuf<uint32_t> d_wb, d_wbtail[2];
+  DevBuf<float> d_sin, d_cos;
+  DevBuf<uint32_t> d_wbpack;            // the two tables x900 as int16 rail pairs (k_wb_rails)
+  DevBuf<uint32_t> d_err;               // k_phase_scan: waits that expired (never, unless the kernel is broken)
   // WBFM: the call's passes run in time slices on three streams (hrfd_mod_process_device)
   static constexpr int kMaxSlices = 32;
   hipStream_t s_scan = nullptr, s_tail = nullptr;  // the recurrence's stream; the stream of every other pass of a sliced call
@@ -41,9 +40,8 @@ struct hrfd_mod
   int scan_kind = 0;                     // test hook: 1 = k_phase_scan<64> / k_phase_scan_plain whatever the bank size, 2 = k_phase_rows (four steps per lane) where k_phase_rows8 would run
   int wb_fused = HRFD_WB_FUSED;          // test hook: 0 = the lookup pass and the x8 cascade as two kernels (rounds 2-5), 1 = k_wb_tail
   // staging for the host entry
-  int16_t *d_in = nullptr;
-  int8_t *d_out = nullptr;
-  size_t cap_in = 0, cap_out = 0;
+  DevBuf<int16_t> d_in;
+  DevBuf<int8_t> d_out;
 };
 
 // the WBFM modulator's last pass over the slice [lo, lo + len) of every channel (len 0: the whole call): Nco::runFast's
@@ -112,7 +110,7 @@ static void phase_scan(hrfd_mod *h, uint32_t *cells, size_t steps, size_t row_st
   }
   else if ((steps & 3) == 0 && (row_stride & 3) == 0)
   {
-    hipLaunchKernelGGL(k_phase_scan<64>, dim3((n_channels + 63) / 64), dim3(kPsThreads), 0, s, cells, steps, row_stride, d_acc, n_channels, h->d_err);
+    hipLaunchKernelGGL(k_phase_scan<64>, dim3((n_channels + 63) / 64), dim3(kPsThreads), 0, s, cells, steps, row_stride, d_acc, n_channels, h->d_err.p);
   }
   else
   {
@@ -145,14 +143,8 @@ static int mod_free(hrfd_mod *h)
     if (h->ev_head[i]) (void)hipEventDestroy(h->ev_head[i]);
     if (h->ev_scan[i]) (void)hipEventDestroy(h->ev_scan[i]);
   }
-  void *ptrs[] = {h->d_tail[0], h->d_tail[1], h->d_lsb, h->d_in, h->d_out, h->d_param, h->d_acc, h->d_phase, h->d_rails,
-                  h->d_wb, h->d_wbtail[0], h->d_wbtail[1], h->d_sin, h->d_cos, h->d_err, h->d_wbpack};
-  for (void *p : ptrs)
-  {
-    if (p) (void)hipFree(p);
-  }
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;                            // with every buffer it owns
   return HRFD_OK;
 }
 
@@ -218,19 +210,22 @@ extern "C" int hrfd_mod_create(int kind, uint32_t n_channels, int device, hrfd_m
   h->h_lsb.assign(n_channels, 1);                        // SsbModulator starts in LSB (SsbModulator.cc ctor)
   const size_t tail_bytes = (size_t)n_channels * 4 * kModTail * sizeof(int16_t);
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_tail[0], tail_bytes);
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_tail[1], tail_bytes);
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_lsb, n_channels);
+  auto alloc = [&e](auto &buf, size_t n) {
+    if (e == hipSuccess && !buf.alloc(n)) e = hipErrorOutOfMemory;
+  };
+  alloc(h->d_tail[0], tail_bytes / sizeof(int16_t));
+  alloc(h->d_tail[1], tail_bytes / sizeof(int16_t));
+  alloc(h->d_lsb, n_channels);
   if (e == hipSuccess) e = hipMemset(h->d_tail[0], 0, tail_bytes);   // zero pipelines == resetModulator()
   if (e == hipSuccess) e = hipMemset(h->d_tail[1], 0, tail_bytes);
   // AmModulator.cc:218 modulationIndex = 0.8; FmModulator.cc:218 frequencyDeviation = 3500, Nco phase 0
   // WbFmModulator.cc:204 frequencyDeviation = 70000
   h->h_param.assign(n_channels, kind == HRFD_MOD_FM ? 3500.0f : kind == HRFD_MOD_WBFM ? 70000.0f : (float)0.8);
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_param, sizeof(float) * n_channels);
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_acc, sizeof(float) * n_channels);
+  alloc(h->d_param, n_channels);
+  alloc(h->d_acc, n_channels);
   if (e == hipSuccess) e = hipMemset(h->d_acc, 0, sizeof(float) * n_channels);
   // [0] waits that expired; [1], [2] counters of the -DHRFD_PS_PROBE diagnostic build of k_phase_scan
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_err, 3 * sizeof(uint32_t));
+  alloc(h->d_err, 3);
   if (e == hipSuccess) e = hipMemset(h->d_err, 0, 3 * sizeof(uint32_t));
   if (kind == HRFD_MOD_WBFM)
   {
@@ -244,8 +239,8 @@ extern "C" int hrfd_mod_create(int kind, uint32_t n_channels, int device, hrfd_m
       ct[i] = cosf(ang);
       ang += inc;
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_sin, sizeof(float) * 16384);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_cos, sizeof(float) * 16384);
+    alloc(h->d_sin, 16384);
+    alloc(h->d_cos, 16384);
     if (e == hipSuccess) e = hipMemcpy(h->d_sin, st.data(), sizeof(float) * 16384, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(h->d_cos, ct.data(), sizeof(float) * 16384, hipMemcpyHostToDevice);
     // WbFmModulator.cc:604-612: iv = cos * 900 (float), (int16_t) -- per table entry instead of per sample
@@ -255,11 +250,11 @@ extern "C" int hrfd_mod_create(int kind, uint32_t n_channels, int device, hrfd_m
       volatile float iv = ct[i] * 900.0f, qv = st[i] * 900.0f;
       pack[i] = ((uint32_t)(int)(short)(int)iv & 0xffffu) | ((uint32_t)(int)(short)(int)qv << 16);
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_wbpack, sizeof(uint32_t) * 16384);
+    alloc(h->d_wbpack, 16384);
     if (e == hipSuccess) e = hipMemcpy(h->d_wbpack, pack.data(), sizeof(uint32_t) * 16384, hipMemcpyHostToDevice);
     for (int k = 0; k < 2; k++)
     {
-      if (e == hipSuccess) e = hipMalloc((void **)&h->d_wbtail[k], sizeof(uint32_t) * 2 * n_channels);
+      alloc(h->d_wbtail[k], (size_t)2 * n_channels);
       if (e == hipSuccess) e = hipMemset(h->d_wbtail[k], 0, sizeof(uint32_t) * 2 * n_channels);
     }
     // The phase recurrence runs one workgroup per 16 channels, one per CU, and every step of it is latency: a
@@ -480,10 +475,10 @@ extern "C" int hrfd_mod_process_device(hrfd_mod *h, const int16_t *d_pcm, uint32
     const size_t samples = (size_t)n_per_channel * h->n_channels;
     const size_t s32 = samples * 32;
     int rc;
-    if (s32 * 4 > h->cap_wb)
+    if (s32 * 4 > h->d_wb.cap)
     {
       HIP_TRY(hipStreamSynchronize(s));
-      if ((rc = grow((void **)&h->d_wb, &h->cap_wb, s32 * 4)) != HRFD_OK) return rc;
+      if ((rc = h->d_wb.grow_bytes(s32 * 4)) != HRFD_OK) return rc;
     }
     // (Cutting the bank into groups of channels on streams of their own buys nothing: the recurrence's time does not
     // depend on the number of channels, so every group's recurrence runs at the same time and the per-sample passes
@@ -563,7 +558,7 @@ extern "C" int hrfd_mod_process_device(hrfd_mod *h, const int16_t *d_pcm, uint32
     {
       hipLaunchKernelGGL(k_mod<HRFD_MOD_WB_HEAD>, dim3(grid), dim3(kModThreads), 0, s, M);
       phase_scan(h, h->d_wb, (size_t)n_per_channel * 32, (size_t)n_per_channel * 32, h->d_acc, h->n_channels, s);
-      M.in = reinterpret_cast<const int16_t *>(h->d_wb);
+      M.in = reinterpret_cast<const int16_t *>(h->d_wb.p);
       M.wbtail = h->d_wbtail[h->cur];
       wb_tail_launch(h, B, M, 0u, 0u, 512u, s);
     }
@@ -580,7 +575,7 @@ extern "C" int hrfd_mod_process_device(hrfd_mod *h, const int16_t *d_pcm, uint32
       HIP_TRY(hipStreamWaitEvent(hs, h->ev_fork, 0));
       HIP_TRY(hipStreamWaitEvent(h->s_scan, h->ev_fork, 0));
       ModParams T = M;
-      T.in = reinterpret_cast<const int16_t *>(h->d_wb);
+      T.in = reinterpret_cast<const int16_t *>(h->d_wb.p);
       T.wbtail = h->d_wbtail[h->cur];
       for (size_t k = 0; k < cuts.size(); k++)
       {
@@ -621,11 +616,11 @@ extern "C" int hrfd_mod_process_device(hrfd_mod *h, const int16_t *d_pcm, uint32
     // baseband rails first (k_am_rails / k_fm_phase + k_fm_rails), then the shared x256 cascade
     const size_t samples = (size_t)n_per_channel * h->n_channels;
     int rc;
-    if (samples * 4 > h->cap_rails || (h->kind == HRFD_MOD_FM && samples * 4 > h->cap_phase))
+    if (samples * 4 > h->d_rails.cap || (h->kind == HRFD_MOD_FM && samples * 4 > h->d_phase.cap))
     {
       HIP_TRY(hipStreamSynchronize(s));
-      if ((rc = grow((void **)&h->d_rails, &h->cap_rails, samples * 4)) != HRFD_OK) return rc;
-      if (h->kind == HRFD_MOD_FM && (rc = grow((void **)&h->d_phase, &h->cap_phase, samples * 4)) != HRFD_OK) return rc;
+      if ((rc = h->d_rails.grow_bytes(samples * 4)) != HRFD_OK) return rc;
+      if (h->kind == HRFD_MOD_FM && (rc = h->d_phase.grow_bytes(samples * 4)) != HRFD_OK) return rc;
     }
     BaseParams B;
     memset(&B, 0, sizeof(B));
@@ -656,11 +651,11 @@ extern "C" int hrfd_mod_process_device(hrfd_mod *h, const int16_t *d_pcm, uint32
       if (!fm_sliced)
       {
         hipLaunchKernelGGL(k_fm_step, dim3(gs), dim3(256), 0, s, B);
-        phase_scan(h, reinterpret_cast<uint32_t *>(h->d_phase), (size_t)n_per_channel, (size_t)n_per_channel, h->d_acc, h->n_channels, s);
+        phase_scan(h, reinterpret_cast<uint32_t *>(h->d_phase.p), (size_t)n_per_channel, (size_t)n_per_channel, h->d_acc, h->n_channels, s);
         // (round 5: cos / sin, x 16000 and the narrowing happen in the cascade's stage-0 load -- k_mod<FM_PHASE> reads the
         //  phases; rounds 1-4 ran a pass of its own, k_fm_rails, in front)
 #if HRFD_FM_FUSED
-        M.in = reinterpret_cast<const int16_t *>(h->d_phase);
+        M.in = reinterpret_cast<const int16_t *>(h->d_phase.p);
         M.libm_fma = libm_variant();
         hipLaunchKernelGGL(k_mod<HRFD_MOD_FM_PHASE>, dim3(grid), dim3(kModThreads), 0, s, M);
 #else
@@ -689,7 +684,7 @@ extern "C" int hrfd_mod_process_device(hrfd_mod *h, const int16_t *d_pcm, uint32
         {
           const uint32_t lo = cut[k], len = cut[k + 1] - lo;
           // (the slices' recurrences follow each other in stream order: the accumulators carry over in d_acc)
-          phase_scan(h, reinterpret_cast<uint32_t *>(h->d_phase) + lo, (size_t)len, (size_t)n_per_channel, h->d_acc, h->n_channels, h->s_scan);
+          phase_scan(h, reinterpret_cast<uint32_t *>(h->d_phase.p) + lo, (size_t)len, (size_t)n_per_channel, h->d_acc, h->n_channels, h->s_scan);
 #if !HRFD_FM_FUSED
           B.lo = lo;
           B.len = len;
@@ -698,7 +693,7 @@ extern "C" int hrfd_mod_process_device(hrfd_mod *h, const int16_t *d_pcm, uint32
           HIP_TRY(hipEventRecord(h->ev_scan[k], h->s_scan));
         }
         // (round 5: no k_fm_rails beside the cascade any more -- the cascade's stage-0 load makes the rails from the phases)
-        M.in = HRFD_FM_FUSED ? reinterpret_cast<const int16_t *>(h->d_phase) : h->d_rails;
+        M.in = HRFD_FM_FUSED ? reinterpret_cast<const int16_t *>(h->d_phase.p) : h->d_rails;
         M.libm_fma = libm_variant();
         for (int k = 0; k < 3; k++)
         {
@@ -724,10 +719,10 @@ extern "C" int hrfd_mod_process_device(hrfd_mod *h, const int16_t *d_pcm, uint32
     // interpolateSignal's own stage-1 table
     const size_t samples = (size_t)n_per_channel * h->n_channels;
     int rc;
-    if (samples * 4 > h->cap_rails)
+    if (samples * 4 > h->d_rails.cap)
     {
       HIP_TRY(hipStreamSynchronize(s));
-      if ((rc = grow((void **)&h->d_rails, &h->cap_rails, samples * 4)) != HRFD_OK) return rc;
+      if ((rc = h->d_rails.grow_bytes(samples * 4)) != HRFD_OK) return rc;
     }
     BaseParams B;
     memset(&B, 0, sizeof(B));
@@ -804,8 +799,8 @@ extern "C" int hrfd_mod_process(hrfd_mod *h, const int16_t *pcm, uint32_t n_per_
   const size_t out_total = (size_t)h->n_channels * n_per_channel * 512;
   int rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
-  if ((rc = grow((void **)&h->d_in, &h->cap_in, in_bytes)) != HRFD_OK) return rc;
-  if ((rc = grow((void **)&h->d_out, &h->cap_out, out_total)) != HRFD_OK) return rc;
+  if ((rc = h->d_in.grow_bytes(in_bytes)) != HRFD_OK) return rc;
+  if ((rc = h->d_out.grow_bytes(out_total)) != HRFD_OK) return rc;
   HIP_TRY(hipMemcpyAsync(h->d_in, pcm, in_bytes, hipMemcpyHostToDevice, h->stream));
   if ((rc = hrfd_mod_process_device(h, h->d_in, n_per_channel, h->d_out, h->stream)) != HRFD_OK) return rc;
   HIP_TRY(hipMemcpyAsync(iq_out, h->d_out, out_total, hipMemcpyDeviceToHost, h->stream));
@@ -824,9 +819,8 @@ struct hrfd_nco
   uint32_t n_channels = 0;
   float sample_rate = 0;
   hipStream_t stream = nullptr;
-  float *d_acc = nullptr, *d_step = nullptr, *d_sin = nullptr, *d_cos = nullptr;
-  float *d_i = nullptr, *d_q = nullptr;
-  size_t cap_out = 0;
+  DevBuf<float> d_acc, d_step, d_sin, d_cos;
+  DevBuf<float> d_i, d_q;              // the outputs of a call: they grow together
   std::vector<float> h_step;
   bool step_dirty = true;
 };
@@ -838,13 +832,8 @@ static int nco_free(hrfd_nco *h)
     return HRFD_OK;
   }
   (void)hipSetDevice(h->device);
-  void *ptrs[] = {h->d_acc, h->d_step, h->d_sin, h->d_cos, h->d_i, h->d_q};
-  for (void *p : ptrs)
-  {
-    if (p) (void)hipFree(p);
-  }
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;                            // with every buffer it owns
   return HRFD_OK;
 }
 
@@ -901,10 +890,10 @@ extern "C" int hrfd_nco_create(uint32_t n_channels, float sample_rate, float fre
     }
   }
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_acc, sizeof(float) * n_channels);
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_step, sizeof(float) * n_channels);
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_sin, sizeof(float) * 16384);
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_cos, sizeof(float) * 16384);
+  if (e == hipSuccess && !(h->d_acc.alloc(n_channels) && h->d_step.alloc(n_channels) && h->d_sin.alloc(16384) && h->d_cos.alloc(16384)))
+  {
+    e = hipErrorOutOfMemory;
+  }
   if (e == hipSuccess) e = hipMemset(h->d_acc, 0, sizeof(float) * n_channels);
   if (e == hipSuccess) e = hipMemcpy(h->d_sin, st.data(), sizeof(float) * 16384, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(h->d_cos, ct.data(), sizeof(float) * 16384, hipMemcpyHostToDevice);
@@ -970,13 +959,11 @@ extern "C" int hrfd_nco_run(hrfd_nco *h, int fast, uint32_t count, float *i_out,
   HIP_TRY(hipSetDevice(h->device));
   const size_t bytes = sizeof(float) * (size_t)h->n_channels * count;
   HIP_TRY(hipStreamSynchronize(h->stream));
-  if (bytes > h->cap_out)
+  if (bytes > std::min(h->d_i.cap, h->d_q.cap))
   {
-    size_t c1 = 0, c2 = 0;
     int rc;
-    if ((rc = grow((void **)&h->d_i, &c1, bytes)) != HRFD_OK) return rc;
-    if ((rc = grow((void **)&h->d_q, &c2, bytes)) != HRFD_OK) return rc;
-    h->cap_out = bytes;
+    if ((rc = h->d_i.grow_bytes(bytes)) != HRFD_OK) return rc;
+    if ((rc = h->d_q.grow_bytes(bytes)) != HRFD_OK) return rc;
   }
   if (h->step_dirty)
   {

@@ -1,12 +1,14 @@
 // hackrfdiags_amd/csrc/hrfd_bank.hip -- the host core of the bank handles (hrfd_ddc, hrfd_duc, hrfd_spec): device and
-// stream ownership, the three ordering rules, the buffers a handle owns, and the argument checks the DDC and the DUC
-// share.  DESIGN.md 3.5a states the rules; hrfd_bank.h holds the parts that need no HIP.
+// stream ownership, the three ordering rules, and the argument checks the DDC and the DUC share.  DESIGN.md 3.5a states
+// the rules; hrfd_bank.h holds the parts that need no HIP, hrfd_buf.h the buffers a handle owns (DevBuf, PinnedBuf: shared
+// with the receive and transmit handles).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <mutex>
 
 #include "hrfd_bank.h"
+#include "hrfd_buf.h"
 #include "hrfd_ddc_tables.h"
 
 #define BANK_TRY(expr)                                                                   \
@@ -106,45 +108,6 @@ struct BankCore
     }
     return HRFD_OK;
   }
-};
-
-// Device and pinned buffers a handle owns: freed with the handle, whatever members it has.
-template <class T>
-struct DevBuf
-{
-  T *p = nullptr;
-  size_t cap = 0;                          // bytes
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf()
-  {
-    if (p) (void)hipFree(p);
-  }
-  bool alloc(size_t n) { return ::grow((void **)&p, &cap, sizeof(T) * n) == HRFD_OK; }
-  int grow(size_t bytes) { return ::grow((void **)&p, &cap, bytes); }   // keeps what is large enough; contents are lost
-  operator T *() const { return p; }
-};
-
-template <class T>
-struct PinnedBuf
-{
-  T *p = nullptr;
-  PinnedBuf() = default;
-  PinnedBuf(const PinnedBuf &) = delete;
-  PinnedBuf &operator=(const PinnedBuf &) = delete;
-  ~PinnedBuf() { release(); }
-  void release()
-  {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-  }
-  bool alloc(size_t n)
-  {
-    release();
-    return hipHostMalloc((void **)&p, sizeof(T) * n, hipHostMallocDefault) == hipSuccess;
-  }
-  operator T *() const { return p; }
 };
 
 // The setters and getters of a handle with one tuning record per channel (the DDC and the DUC), under `who`, the public

@@ -594,8 +594,8 @@ extern "C" int hrfd_ddc_process(hrfd_ddc *d, const int8_t *captures, uint32_t ou
   hipStream_t s = d->core.stream;
   BANK_TRY(d->core.drain());
   const size_t in_bytes = (size_t)d->n_captures * d->R * out_bytes, out_total = (size_t)d->n_channels * out_bytes;
-  BANK_TRY(d->d_in.grow(in_bytes));
-  BANK_TRY(d->d_out.grow(out_total));
+  BANK_TRY(d->d_in.grow_bytes(in_bytes));
+  BANK_TRY(d->d_out.grow_bytes(out_total));
   HIP_TRY(hipMemcpyAsync(d->d_in, captures, in_bytes, hipMemcpyHostToDevice, s));
   BANK_TRY(ddc_launch(d, d->d_in, (uint64_t)d->R * out_bytes, out_bytes, d->d_out, out_bytes, s));
   HIP_TRY(hipMemcpyAsync(out, d->d_out, out_total, hipMemcpyDeviceToHost, s));
@@ -632,11 +632,11 @@ extern "C" int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captur
   const uint32_t C = d->n_channels;
   const size_t units = (size_t)C * n_blocks;
   HIP_TRY(hipStreamSynchronize(s));
-  BANK_TRY(d->d_rx.grow((size_t)C * out_bytes));
+  BANK_TRY(d->d_rx.grow_bytes((size_t)C * out_bytes));
   if (d_magnitude == nullptr || d_signal_allowed == nullptr)
   {
     // the rx launches always write both: scratch rows for the ones the caller does not want
-    BANK_TRY(d->d_scratch_mag.grow(units * 5));
+    BANK_TRY(d->d_scratch_mag.grow_bytes(units * 5));
   }
   uint32_t *mag = d_magnitude ? d_magnitude : (uint32_t *)d->d_scratch_mag.p;
   uint8_t *allowed = d_signal_allowed ? d_signal_allowed : d->d_scratch_mag + units * 4;

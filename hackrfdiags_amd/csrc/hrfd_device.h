@@ -49,6 +49,14 @@ constexpr int kQuadRow = 129;                 // first-quadrant table (theta_qua
 constexpr int kQuadEntries = 129 * 129;
 constexpr int kQuadDwords = 16644;            // padded to 16-byte copies
 
+// build switches of k_rx_wbfm_flow (hrfd_rx_flow.hip) that the host's launch plan (hrfd_rx_plan.h) reads as well
+#ifndef HRFD_FLOW_WARM_TILES
+#define HRFD_FLOW_WARM_TILES 2      /* warm-up of the recurrence tiles, in tiles of 64 samples (2: ~7e-4 of the tiles are repaired in place) */
+#endif
+#ifndef HRFD_FLOW_SPLIT
+#define HRFD_FLOW_SPLIT 1           /* 0 builds the round-4 WBFM kernel (hrfd_rx_flow.hip) */
+#endif
+
 // carried history sizes of the integer stages ("carried state")
 constexpr int kWbS = 4, kWbU = 8, kWbV = 38;  // WBFM: last N-M inputs of D(8,4), D(12,4), D(40,2)
 constexpr int kFmTail = 704;                  // FM:  iq256 samples (>= 684)

@@ -642,8 +642,8 @@ extern "C" int hrfd_duc_process(hrfd_duc *d, const int8_t *channels, uint32_t in
   hipStream_t s = d->core.stream;
   BANK_TRY(d->core.drain());
   const size_t in_total = (size_t)d->n_channels * in_bytes, out_total = (size_t)d->n_captures * d->R * in_bytes;
-  BANK_TRY(d->d_in.grow(in_total));
-  BANK_TRY(d->d_out.grow(out_total));
+  BANK_TRY(d->d_in.grow_bytes(in_total));
+  BANK_TRY(d->d_out.grow_bytes(out_total));
   HIP_TRY(hipMemcpyAsync(d->d_in, channels, in_total, hipMemcpyHostToDevice, s));
   BANK_TRY(duc_launch(d, d->d_in, in_bytes, in_bytes, d->d_out, (uint64_t)d->R * in_bytes, s));
   HIP_TRY(hipMemcpyAsync(captures, d->d_out, out_total, hipMemcpyDeviceToHost, s));
@@ -675,7 +675,7 @@ extern "C" int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pc
   if (need > d->d_tx.cap)
   {
     HIP_TRY(hipStreamSynchronize(d->core.last_stream));  // the last launch may still read the old buffer
-    BANK_TRY(d->d_tx.grow(need));
+    BANK_TRY(d->d_tx.grow_bytes(need));
   }
   // the modulator overwrites the buffer the handle's last launch reads: behind it on the device
   BANK_TRY(d->core.order_behind_last(s));

@@ -38,9 +38,7 @@
 #ifndef HRFD_FLOW_SVC
 #define HRFD_FLOW_SVC 4
 #endif
-#ifndef HRFD_FLOW_WARM_TILES
-#define HRFD_FLOW_WARM_TILES 2      /* warm-up of the recurrence tiles, in tiles of 64 samples (2: ~7e-4 of the tiles are repaired in place) */
-#endif
+// (HRFD_FLOW_WARM_TILES, the warm-up of the recurrence tiles: hrfd_device.h -- the host's launch plan reads it too)
 #ifndef HRFD_FLOW_SVC_PRIO
 #define HRFD_FLOW_SVC_PRIO 3
 #endif
@@ -49,9 +47,7 @@
 // the service waves, which keep a tile's v in REGISTERS through the partial sum, the warm-up passes and the tile
 // itself, and the freed LDS holds a first-QUADRANT atan2 table (theta_quad) and a ring of 512 tiles.
 // -DHRFD_FLOW_SPLIT=0 builds the round-4 kernel (the A/B of profiles/r5_flow_split_ab.txt).
-#ifndef HRFD_FLOW_SPLIT
-#define HRFD_FLOW_SPLIT 1
-#endif
+// (HRFD_FLOW_SPLIT itself: hrfd_device.h -- the host's launch plan reads it too)
 #ifndef HRFD_FLOW_SVC_WB
 #define HRFD_FLOW_SVC_WB 6          /* service waves of the re-split WBFM kernel (they do a third of the work now) */
 #endif

@@ -613,7 +613,7 @@ static int spec_launch(hrfd_spec *s, const int8_t *d_captures, uint64_t capture_
             return fail(HRFD_ENODEV, "hrfd_spec: no pinned memory for %zu bands: %s", cap, hipGetErrorString(hipGetLastError()));
           }
           s->cap_stage_bands = cap;
-          BANK_TRY(s->d_bands.grow(sizeof(SpecBandDev) * cap));
+          BANK_TRY(s->d_bands.grow_bytes(sizeof(SpecBandDev) * cap));
         }
         for (uint32_t b = 0; b < K; b++)
         {
@@ -688,12 +688,12 @@ extern "C" int hrfd_spec_process(hrfd_spec *s, const int8_t *captures, uint32_t 
   }
   const size_t row = 2 * (size_t)s->N * n_frames, in_total = row * s->n_captures;
   const size_t p_total = sizeof(uint64_t) * (size_t)s->n_captures * s->N;
-  BANK_TRY(s->d_in.grow(in_total));
-  BANK_TRY(s->d_power.grow(p_total));
+  BANK_TRY(s->d_in.grow_bytes(in_total));
+  BANK_TRY(s->d_power.grow_bytes(p_total));
   if (K > 0)
   {
-    BANK_TRY(s->d_band_power.grow(sizeof(uint64_t) * K));
-    BANK_TRY(s->d_present.grow(K));
+    BANK_TRY(s->d_band_power.grow_bytes(sizeof(uint64_t) * K));
+    BANK_TRY(s->d_present.grow_bytes(K));
   }
   HIP_TRY(hipMemcpyAsync(s->d_in, captures, in_total, hipMemcpyHostToDevice, st));
   BANK_TRY(spec_launch(s, s->d_in, row, n_frames, s->d_power, s->d_band_power, s->d_present, K, st));

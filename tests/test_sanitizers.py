@@ -45,6 +45,38 @@ def test_bank_core_under_sanitizers(tmp_path):
     assert r.returncode == 0 and "san_bank ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
 
 
+def test_rx_plan_under_sanitizers(tmp_path):
+    """The HIP-free part of the receive launch (hackrfdiags_amd/csrc/hrfd_rx_plan.h: geometry, channel lists, the plan)
+    compiled into tests/cpp/san_rx_plan.cc under -fsanitize=address,undefined and run: the lists against brute force, the
+    longest plans (eleven steps of the twelve the plan holds), refusals with their texts.  tests/test_rx_plan_model.py runs
+    the same program over its full grids."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "san_rx_plan")
+    cmd = ["g++", "-x", "c++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+           os.path.join(HERE, "cpp", "san_rx_plan.cc")]
+    b = subprocess.run(cmd, capture_output=True, text=True, cwd=os.path.join(HERE, "cpp"))
+    if b.returncode != 0 and ("cannot find" in b.stderr or "unrecognized" in b.stderr):
+        pytest.skip("this toolchain has no runtime for -fsanitize=address,undefined")
+    assert b.returncode == 0, b.stderr[-2000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1")
+    r = subprocess.run([exe, "lists"], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0 and "san_rx_plan lists ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
+    # 1 NONE, 3 AM, 4 FM, 8 WBFM, 2 LSB, 2 USB; 16 blocks of 16384 samples; a threshold that lets gates close: the FIR
+    # kinds on their block kernels (three launches), the WBFM flow launch with its gated one, mode NONE, five finish launches.
+    # Then an empty bank.
+    plans = "1 3 4 8 2 2 16 16384 0 0 3 0 0 0 0 2 -1 -1 1 0 1 1 1 0 0\n" + "0 0 0 0 0 0 1 64 0 0 3 0 0 0 0 2 -1 -1 1 0 1 1 1 0 0\n"
+    r = subprocess.run([exe, "plan"], input=plans, capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
+    lines = r.stdout.splitlines()
+    assert lines[0] == "case 0 11" and lines[12] == "case 1 0" and len(lines) == 13, lines
+    assert [x.split()[0] for x in lines[1:12]] == ["fir_as", "post_as", "fir_fm_arith", "flow_wb", "gated_wb", "blocks_none"] + ["finish"] * 5
+    r = subprocess.run([exe, "geom"], input="262146 1 262146 0 1 0 0 0 512\n1024 1 1024 0 1 0 0 0 512\n", capture_output=True, text=True,
+                       env=env, timeout=300)
+    assert r.returncode == 0 and r.stdout.splitlines() == ["-1 block_bytes must be even, > 0 and <= 262144 (got 262146)",
+                                                           "0 0 64 3 5 19 -1266 1280"], (r.stdout, r.stderr[-3000:])
+
+
 SHIM = os.path.join(os.path.dirname(HERE), "hackrfdiags_amd", "csrc", "shim")
 
 
