@@ -134,6 +134,15 @@ class Rx:
         check(self.L.hrfd_rx_debug_ragged(self.h, C.byref(off), C.byref(n)), "hrfd_rx_debug_ragged")
         return bool(off.value), int(n.value)
 
+    def debug_mag_skipped(self) -> int:
+        """launches so far that ran on the WBFM flow kernel's instantiation without the squelch magnitude (no magnitude
+        buffer passed and no gate of the bank could close)"""
+        n = C.c_ulonglong(0)
+        fn = self.L.hrfd_rx_debug_mag_skipped
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        check(fn(self.h, C.byref(n)), "hrfd_rx_debug_mag_skipped")
+        return int(n.value)
+
     def debug_set_run_len(self, blocks: int):
         """consecutive blocks of a channel per WBFM workgroup (0 = automatic)"""
         check(self.L.hrfd_rx_debug_set_run_len(self.h, int(blocks)), "hrfd_rx_debug_set_run_len")

@@ -139,12 +139,7 @@ static bool build_atan_quadrant(const float *lut, uint32_t *out)
 
 static void build_dbfs(int32_t *out)
 {
-  for (int i = 1; i <= 256; i++)
-  {
-    const float db = 20 * log10f((float)i);
-    out[i] = (int32_t)db;
-  }
-  out[0] = out[1];
+  rx_build_dbfs(out);                                      // (hrfd_rx_plan.h: tests/cpp/san_rx_mag.cc reads the same table)
 }
 
 extern "C" int hrfd_atan2_table(float *out)
@@ -271,6 +266,7 @@ struct hrfd_rx
   bool rag_built = false;              // k_rag_expand has run (ChanState -> RagState)
   DevBuf<RagState> d_rag;
   uint64_t ragged_launches = 0;        // launches that ran on k_rx_ragged (diagnostic: hrfd_rx_debug_ragged)
+  uint64_t mag_skipped_launches = 0;   // launches of k_rx_wbfm_flow<.., MAG = false> (diagnostic: hrfd_rx_debug_mag_skipped)
 };
 
 static int rx_free(hrfd_rx *h)
@@ -688,6 +684,8 @@ static void rx_fill_params(hrfd_rx *h, const RxCall &c, const RxGeometry &g, RxP
   P.flow_hal = 1536;           // >= 768 + 64 * (warm_tiles + seed_terms + 1), whole units
   P.flow_seed_ct = (float)pow(-(double)DEEMPH_A1, 64.0);
   P.dbg = nullptr;
+  // (wbfm_max_threshold is the snapshot's: rx_snapshot runs in front of this)
+  P.mag_unobservable = rx_magnitude_unobservable(h->wbfm_max_threshold, c.gain_db, c.d_magnitude != nullptr) ? 1 : 0;
 
   EpilogueParams E;
   memset(&E, 0, sizeof(E));
@@ -847,7 +845,18 @@ static int rx_execute(hrfd_rx *h, const RxPlan &plan, const RxParams &base, cons
       case kRxFlowAsDump: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, true, 14>), grid, block, 0, s, P); break;
       case kRxFlowFm: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false, 2>), grid, block, 0, s, P); break;
       case kRxFlowFmDump: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, true, 2>), grid, block, 0, s, P); break;
-      case kRxFlowWb: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false>), grid, block, 0, s, P); break;
+      case kRxFlowWb:
+#if HRFD_FLOW_NOMAG
+        if (P.mag_unobservable != 0)
+        {
+          // nobody can see the block magnitudes: the instantiation whose stream waves do not compute them
+          hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false, 3, false>), grid, block, 0, s, P);
+          h->mag_skipped_launches++;
+          break;
+        }
+#endif
+        hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false>), grid, block, 0, s, P);
+        break;
       case kRxFlowWbDump: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, false, true>), grid, block, 0, s, P); break;
       case kRxGatedWb: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, true, false>), grid, block, 0, s, P); break;
       case kRxGatedFm: hipLaunchKernelGGL((k_rx_wbfm_flow<HRFD_FLOW_SVC, true, false, 2>), grid, block, 0, s, P); break;

@@ -370,6 +370,17 @@ extern "C" int hrfd_rx_debug_ragged(hrfd_rx *h, int *offgrid, unsigned long long
   return HRFD_OK;
 }
 
+// launches of this handle that ran on k_rx_wbfm_flow<.., MAG = false> (no block magnitudes: rx_magnitude_unobservable)
+extern "C" int hrfd_rx_debug_mag_skipped(hrfd_rx *h, unsigned long long *launches)
+{
+  if (h == nullptr || launches == nullptr)
+  {
+    return fail(HRFD_EINVAL, "NULL");
+  }
+  *launches = h->mag_skipped_launches;
+  return HRFD_OK;
+}
+
 // test hook: 0 = no gated second pass on the device; a channel with a closed gate in a batch stays failed (the host replays it)
 extern "C" int hrfd_rx_debug_set_gated(hrfd_rx *h, int on)
 {

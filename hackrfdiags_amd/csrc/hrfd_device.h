@@ -56,6 +56,14 @@ constexpr int kQuadDwords = 16644;            // padded to 16-byte copies
 #ifndef HRFD_FLOW_SPLIT
 #define HRFD_FLOW_SPLIT 1           /* 0 builds the round-4 WBFM kernel (hrfd_rx_flow.hip) */
 #endif
+// A WBFM batch whose caller wants no magnitudes and whose gates cannot close (rx_magnitude_unobservable, hrfd_rx_plan.h)
+// runs on k_rx_wbfm_flow<.., MAG = false>: 0 never (that instantiation is not built, every launch computes the sums: the
+// behaviour before the parameter existed, for an A/B), 1 the stream waves leave out the squelch magnitude and its sums,
+// 2 (default) the per-block bookkeeping as well -- at 256 channels within the run-to-run spread of 1, which holds the
+// whole gain there (profiles/r7_nomag_ab.txt: 0.2077 against 0.2075 ms, alternating runs on one box)
+#ifndef HRFD_FLOW_NOMAG
+#define HRFD_FLOW_NOMAG 2
+#endif
 
 // carried history sizes of the integer stages ("carried state")
 constexpr int kWbS = 4, kWbU = 8, kWbV = 38;  // WBFM: last N-M inputs of D(8,4), D(12,4), D(40,2)
@@ -183,6 +191,7 @@ struct RxParams
   int32_t self_finish;         // ... when this is set (also k_rx_fir<FM> and k_rx_post: they finish their channels themselves)
   int32_t flow_hal;            // k_rx_wbfm_flow: history samples in front of a run that does not start the call (multiple of 512)
   float flow_seed_ct;          // k_rx_wbfm_flow: (-a1)^64
+  int32_t mag_unobservable;    // nobody can see the block magnitudes of this launch (rx_magnitude_unobservable): kRxFlowWb may leave them out
   unsigned long long *dbg;     // optional [grid][kDbgSlots] s_memtime stamps at phase boundaries (diagnostic builds of bench only)
 };
 

@@ -473,10 +473,18 @@ static_assert(384 + kCoopRows <= kFRing2 || kFRing2 < 512, "the scratch area fit
 //   service_waves_wbfm()    waves 0 .. SVC-1, WBFM: v -> recurrence tiles -> integer stages -> PCM
 //   finish()                the channel's verdict and commit (from LDS when the channel was this workgroup's alone)
 // Everything is inlined into the kernel; the object is scalarised by the compiler (no scratch: tools/kinfo.sh).
-template <int SVC, bool GATED, bool DUMP, int MODE>
+// MAG = false (the plain WBFM batch only; rx_magnitude_unobservable, hrfd_rx_plan.h): nobody can see the block magnitudes
+// -- the caller passed no buffer for them and every threshold of the bank is at or below the detector's lowest level, so
+// dbfs >= cfg.threshold holds for every block whatever its sum is.  The stream waves then make no magnitude() call and no
+// sum, every block's word is "present, magnitude 0", and (HRFD_FLOW_NOMAG >= 2) the blocks are not counted either: their
+// words are preset and nothing waits for them.  PCM, n_pcm, signal_allowed and the committed state see the present bits
+// only (finish(), finish_channel), and those are the same: all set.
+template <int SVC, bool GATED, bool DUMP, int MODE, bool MAG = true>
 struct Flow
 {
   static_assert(MODE == 3 || MODE == 2 || MODE == 14, "WBFM, FM, AM / SSB");
+  static_assert(MAG || (MODE == 3 && !GATED && !DUMP), "only the plain WBFM batch leaves the magnitude out");
+  static constexpr bool kNoBlocks = !MAG && (HRFD_FLOW_NOMAG >= 2);   // no block bookkeeping in the unit loop
   typedef FlowLds<MODE> Lds;
   static constexpr bool kWb = (MODE == 3);
   static constexpr bool kSplit = Lds::kSplit;            // WBFM, re-split (round 5): (q, i) pairs in the ring, theta in the service waves
@@ -661,6 +669,10 @@ struct Flow
 
     // tables and control words
     magl[0][tid] = 0u;
+    if (kNoBlocks && tid < 64)
+    {
+      blkout[tid] = 0x80000000u;                           // every block present, magnitude 0: nobody finishes a block
+    }
     if (kAtan)
     {
       for (int i = tid; i < kCorrBytes / 4; i += kThreads)
@@ -911,18 +923,27 @@ struct Flow
       }
       if (pend && __builtin_amdgcn_readfirstlane((int)pend_nth) == upb - 1)
       {
-        uint32_t total = magl[pend_slot][lane];
-        magl[pend_slot][lane] = 0u;
-        for (int off = 32; off > 0; off >>= 1)
+        uint32_t total = 0u;
+        if (MAG)
         {
-          total += __shfl_down(total, off);
+          total = magl[pend_slot][lane];
+          magl[pend_slot][lane] = 0u;
+          for (int off = 32; off > 0; off >>= 1)
+          {
+            total += __shfl_down(total, off);
+          }
         }
         if (lane == 0)
         {
-          const uint32_t mean_mag = total / (uint32_t)n256;
-          int32_t dbfs = (int32_t)dbfs8[min(mean_mag, 127u)] - 42;
-          dbfs = (int32_t)((uint32_t)dbfs - P.gain_db);
-          blkout[pend_blk & 63] = mean_mag | ((dbfs >= cfg.threshold) ? 0x80000000u : 0u);
+          uint32_t word = 0x80000000u;                   // !MAG: no gate can close -- present, and no magnitude
+          if (MAG)
+          {
+            const uint32_t mean_mag = total / (uint32_t)n256;
+            int32_t dbfs = (int32_t)dbfs8[min(mean_mag, 127u)] - 42;
+            dbfs = (int32_t)((uint32_t)dbfs - P.gain_db);
+            word = mean_mag | ((dbfs >= cfg.threshold) ? 0x80000000u : 0u);
+          }
+          blkout[pend_blk & 63] = word;
           lds_st(&ctl[8 + pend_slot], 0u);
           atomicOr(&ctl[kCtlBlk + ((pend_blk >> 5) & 1)], 1u << (pend_blk & 31));   // the slot is block pend_blk + 16's now
           atomicAdd(&ctl[3], 1u);                        // blocks finished
@@ -1112,7 +1133,7 @@ struct Flow
       auto store_pairs = [&](const uint32_t (&mx)[4], uint32_t *d) {
         const uint32_t w0 = __builtin_amdgcn_perm(mx[1], mx[0], 0x06040200u), w1 = __builtin_amdgcn_perm(mx[3], mx[2], 0x06040200u);
         reinterpret_cast<uint2 *>(d)[0] = make_uint2(w0, w1);
-        mag4 = magnitude(mx[0]) + magnitude(mx[1]) + magnitude(mx[2]) + magnitude(mx[3]);
+        mag4 = MAG ? magnitude(mx[0]) + magnitude(mx[1]) + magnitude(mx[2]) + magnitude(mx[3]) : 0u;
         if (DUMP)
         {
           iqb[0] = w0 ^ 0x80808080u;
@@ -1233,7 +1254,7 @@ struct Flow
       {
         edges[u & (kFEdges - 1)][lane] = (lane == 0) ? e0 : (lane == 1) ? e1 : (lane == 2) ? e2 : e3;
       }
-      const bool counted = !GATED && u >= (hal >> 9);    // history in front of the run is not in any block's squelch sum (GATED: the batch launch's sums stand)
+      const bool counted = !GATED && !kNoBlocks && u >= (hal >> 9);    // history in front of the run is not in any block's squelch sum (GATED: the batch launch's sums stand)
       int slot = 0;
       if (counted)
       {
@@ -1262,7 +1283,10 @@ struct Flow
             break;
           }
         }
-        atomicAdd(&magl[slot][lane], magsum);
+        if (MAG)
+        {
+          atomicAdd(&magl[slot][lane], magsum);
+        }
       }
       // LDS executes a wave's operations in order: the flag and the block's unit count go out behind the data
       // without waiting for anything; the count's old value is looked at one unit later (pend_*)
@@ -1297,18 +1321,24 @@ struct Flow
       // every stream wave is through its units by now or about to be: wait for the last blocks, then the
       // squelch inputs of the whole run go out
       const uint32_t nb = b_end - b_first;
-      FlowSpin sp;
-      while (lds_ld(&ctl[3]) != nb && !sp.expired(P, ctl, fail_code, 2))
+      if (!kNoBlocks)
       {
-        __builtin_amdgcn_s_sleep(2);
+        FlowSpin sp;
+        while (lds_ld(&ctl[3]) != nb && !sp.expired(P, ctl, fail_code, 2))
+        {
+          __builtin_amdgcn_s_sleep(2);
+        }
+        lds_order();
       }
-      lds_order();
       for (uint32_t i = lane; i < nb; i += 64)
       {
-        const uint32_t w = blkout[i & 63];
+        const uint32_t w = kNoBlocks ? 0x80000000u : blkout[i & 63];
         const uint32_t b = b_first + i;
-        P.magnitude[(size_t)c * P.out_blocks + P.out_b0 + b] = w & 0x7fffffffu;
-        P.present[(size_t)c * P.n_blocks + b] = (uint8_t)(w >> 31);
+        if (MAG)
+        {
+          P.magnitude[(size_t)c * P.out_blocks + P.out_b0 + b] = w & 0x7fffffffu;
+        }
+        P.present[(size_t)c * P.n_blocks + b] = (uint8_t)(w >> 31);   // (!MAG: 1 -- the finisher of a channel cut into runs reads it)
       }
     }
 #ifdef HRFD_FLOW_PROBE
@@ -3099,12 +3129,12 @@ struct Flow
   }
 };
 
-template <int SVC_, bool GATED, bool DUMP, int MODE>
+template <int SVC_, bool GATED, bool DUMP, int MODE, bool MAG = true>
 __device__ __forceinline__ void flow_body(const RxParams &P, uint32_t *const lds)
 {
   // (the re-split WBFM chain gives its service waves a third of the work: more of them)
   constexpr int SVC = FlowLds<MODE>::kSplit ? HRFD_FLOW_SVC_WB : SVC_;
-  Flow<SVC, GATED, DUMP, MODE> F(P, lds);
+  Flow<SVC, GATED, DUMP, MODE, MAG> F(P, lds);
   if (!F.setup())
   {
     return;
@@ -3128,11 +3158,11 @@ __device__ __forceinline__ void flow_body(const RxParams &P, uint32_t *const lds
   F.finish();
 }
 
-template <int SVC, bool GATED, bool DUMP, int MODE = 3>
+template <int SVC, bool GATED, bool DUMP, int MODE = 3, bool MAG = true>
 __global__ __launch_bounds__(kThreads, 4) void k_rx_wbfm_flow(const RxParams P)
 {
   __shared__ __attribute__((aligned(16))) uint32_t lds[FlowLds<MODE>::kTotal];
-  flow_body<SVC, GATED, DUMP, MODE>(P, lds);
+  flow_body<SVC, GATED, DUMP, MODE, MAG>(P, lds);
 }
 
 // A bank of several modes (BASELINE config 3) as ONE launch: one persistent workgroup per channel whatever its mode,
@@ -3176,5 +3206,8 @@ template __global__ void k_rx_wbfm_flow<HRFD_FLOW_SVC, true, false, 2>(const RxP
 template __global__ void k_rx_wbfm_flow<HRFD_FLOW_SVC, true, false, 14>(const RxParams);
 template __global__ void k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false, 2>(const RxParams);
 template __global__ void k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false, 14>(const RxParams);
+#if HRFD_FLOW_NOMAG
+template __global__ void k_rx_wbfm_flow<HRFD_FLOW_SVC, false, false, 3, false>(const RxParams);
+#endif
 
 } // namespace hrfd

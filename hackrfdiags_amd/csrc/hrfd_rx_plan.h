@@ -5,6 +5,7 @@
 // tests/rx_plan_model.py states the same rules a second time); the includer declares
 // `int fail(int code, const char *fmt, ...)` and the HRFD_* codes first.
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -165,6 +166,29 @@ inline int32_t rx_max_threshold(const ChanCfg *cfg, uint32_t n)
     }
   }
   return t;
+}
+
+// The detector's table: 20 log10(i) truncated, entry 0 as entry 1 (DbfsCalculator.cc:58-65); 257 entries.  The kernels
+// look a block's mean magnitude (at most 127: a 7-bit full scale) up in it and take 42 and the gain off.
+inline void rx_build_dbfs(int32_t *out)
+{
+  for (int i = 1; i <= 256; i++)
+  {
+    const float db = 20 * log10f((float)i);
+    out[i] = (int32_t)db;
+  }
+  out[0] = out[1];
+}
+
+// Can anybody see the block magnitudes of a launch?  Not when the caller passed no buffer for them AND no gate of the
+// bank can close: the detector's lowest level is 0 - 42 - gain_db dBFS, every block is `present` whatever its sum is, and
+// PCM, n_pcm, signal_allowed and the committed state follow from the present bits alone.  The comparison is rx_plan's own
+// for `gated` -- in 64 bits, so that a gain at which the kernels' 32-bit subtraction wraps counts as "a gate can close" --
+// without the gated_pass knob and the 64-block clause: a handle whose gated pass is switched off still needs its sums
+// when a gate can close (the channel fails on them and is replayed).
+inline bool rx_magnitude_unobservable(int32_t max_threshold, uint32_t gain_db, bool caller_wants_magnitude)
+{
+  return !caller_wants_magnitude && !((int64_t)max_threshold > -42 - (int64_t)gain_db);
 }
 
 // ------------------------------------------------------------------ the plan

@@ -101,7 +101,10 @@ int hrfd_rx_reset_demod(hrfd_rx *h, uint32_t channel, int mode);
  *   pcm           [n_channels][n_blocks][hrfd_rx_pcm_capacity(block_bytes)] int16: a row holds n_pcm samples (out)
  *   n_pcm         [n_channels][n_blocks] samples actually produced (block_bytes/512 for whole multiples of 512 on an
  *                 open gate); 0 when squelched / mode NONE (the reference then makes no PCM callback)   (out)
- *   magnitude     [n_channels][n_blocks] Squelch::getSignalMagnitude() (out, may be NULL)
+ *   magnitude     [n_channels][n_blocks] Squelch::getSignalMagnitude() (out, may be NULL = not wanted.  A device-entry
+ *                 batch of WBFM channels given NULL does not compute it at all while no squelch gate of the bank can
+ *                 close -- every threshold <= -42 - gain_db, the reference's default of -200 among them: PCM, n_pcm,
+ *                 signal_allowed and the carried state do not depend on it then, and the launch is faster for it)
  *   signal_allowed[n_channels][n_blocks] Squelch::run() result       (out, may be NULL)
  *   iq256k_opt    [n_channels][n_blocks][hrfd_rx_iq256_capacity(block_bytes)] decimatedData after the Fs/4 mix -- what
  *                 `enable iqdump` sends by UDP; block_bytes/8 bytes for multiples of 16   (out, may be NULL)

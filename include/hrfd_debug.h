@@ -40,6 +40,9 @@ int hrfd_rx_debug_chk(hrfd_rx *h, float *pub, float *spec, uint32_t n);
 /* *offgrid: the handle was given a block that is not a whole number of PCM samples (512 bytes; inner API 64) and keeps
  * its state in RagState since; *launches: launches so far that ran on k_rx_ragged (hrfd_rx_ragged.hip) */
 int hrfd_rx_debug_ragged(hrfd_rx *h, int *offgrid, unsigned long long *launches);
+/* *launches: launches so far that ran on the WBFM flow kernel's instantiation without the squelch magnitude (no magnitude
+ * buffer was passed and no gate of the bank could close: hrfd.h at `magnitude`) */
+int hrfd_rx_debug_mag_skipped(hrfd_rx *h, unsigned long long *launches);
 
 /* the device's restatement of glibc's sinf / cosf (hrfd_tx_kernels.hip: glibc_sincosf*), evaluated on the current
  * device; host pointers.  variant 0 / 1: without / with fused multiply-adds -- selects the template, not what the host's

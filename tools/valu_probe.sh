@@ -46,7 +46,7 @@ for line in txt:
     f = line.split()
     if len(f) >= 3 and f[0] in want and f[-1].startswith("mean="):
         summ[f[0]] = float(f[-1][5:])
-json.dump({"kernel_code_tag": bench.kernel_code_tag(), "kernel": "k_rx_wbfm_flow<4, false, false, 3>, 256 channels x 16 blocks",
+json.dump({"kernel_code_tag": bench.kernel_code_tag(), "kernel": "k_rx_wbfm_flow<4, false, false, 3, false> (the bench passes no magnitude buffer: MAG = false), 256 channels x 16 blocks",
            "how": "tools/valu_probe.sh: rocprofv3 --pmc (derived and raw SQ counters, PMC-only passes of bench.py --steps 6 --warmup 2), mean over the launches", "counters": summ},
           open(O + "/valu_probe.json", "w"), indent=1)
 PY
