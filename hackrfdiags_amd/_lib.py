@@ -203,6 +203,16 @@ def load() -> C.CDLL:
         L.hrfd_spec_n_bands.argtypes = [_vp, _u32p]
         L.hrfd_spec_process.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp, _vp]
         L.hrfd_spec_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]
+    if hasattr(L, "hrfd_cal_create"):                      # (an older build named by HRFD_LIB has no conditioner bank)
+        _i64p = C.POINTER(C.c_int64)
+        L.hrfd_cal_create.argtypes = [C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_cal_destroy.argtypes = [_vp]
+        L.hrfd_cal_set_correction.argtypes = [_vp, C.c_uint32, _i32p, _i16p]
+        L.hrfd_cal_get_correction.argtypes = [_vp, C.c_uint32, _i32p, _i16p]
+        L.hrfd_cal_process.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp]
+        L.hrfd_cal_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp]
+        L.hrfd_cal_solve.argtypes = [_i64p, _i32p, _i16p]
+        L.hrfd_cal_debug_set_workgroups.argtypes = [_vp, C.c_int]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

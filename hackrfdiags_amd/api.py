@@ -525,7 +525,7 @@ def ddc_step(offset_hz: float, decimation: int) -> int:
 
 
 class _Bank:
-    """What Ddc, Duc and Spectrum share: the handle of hrfd_<_prefix>_create and its release."""
+    """What Ddc, Duc, Spectrum and Conditioner share: the handle of hrfd_<_prefix>_create and its release."""
     _prefix = ""
 
     def _create(self, *args):
@@ -801,6 +801,80 @@ class Spectrum(_Bank):
         check(self.L.hrfd_spec_process_device(self.h, _ptr(d_captures), int(capture_stride), int(n_frames), _ptr(d_power),
                                               _ptr(d_band_power), _ptr(d_present), _ptr(stream)),
               "hrfd_spec_process_device")
+
+
+CAL_IDENTITY = (16384, 0, 0, 16384)
+CAL_DEGENERATE = 1
+
+
+def cal_sum(moments_list) -> np.ndarray:
+    """the word-wise sum (modulo 2^64) of the moments of several calls: int64 [..., 8] each, all of one shape"""
+    total = None
+    for m in moments_list:
+        u = np.ascontiguousarray(m, dtype=np.int64).view(np.uint64)
+        total = u.copy() if total is None else total + u
+    if total is None:
+        raise ValueError("cal_sum needs at least one set of moments")
+    return total.view(np.int64)
+
+
+def cal_solve(moments):
+    """hrfd_cal_solve over one capture's moments (int64 [8]): (dc int32 [2] in Q8, m int16 [4] in Q14, solved); solved is
+    False where the moments are degenerate and m is the identity.  Host only: needs no device."""
+    L = _lib.load()
+    mom = np.ascontiguousarray(moments, dtype=np.int64)
+    if mom.shape != (8,):
+        raise ValueError(f"cal_solve takes one capture's 8 moments, got shape {mom.shape}")
+    dc, m = np.zeros(2, dtype=np.int32), np.zeros(4, dtype=np.int16)
+    rc = L.hrfd_cal_solve(mom.ctypes.data_as(C.POINTER(C.c_int64)), dc.ctypes.data_as(C.POINTER(C.c_int32)),
+                          m.ctypes.data_as(C.POINTER(C.c_int16)))
+    if rc not in (0, CAL_DEGENERATE):
+        check(rc, "hrfd_cal_solve")
+    return dc, m, rc == 0
+
+
+class Conditioner(_Bank):
+    """A bank of capture conditioners (hrfd_cal_*): n_captures int8 IQ captures in, the same captures with one Q8 offset
+    taken off and one 2 x 2 Q14 matrix applied per capture out, and / or the moments of the raw input (cal_solve)."""
+
+    _prefix = "cal"
+
+    def __init__(self, n_captures: int, device: int = -1):
+        self.W = int(n_captures)
+        self._create(self.W, device)
+
+    def set_correction(self, dc=None, m=None, capture=ALL):
+        """dc: 2 values in Q8, None = (0, 0); m: (m_ii, m_iq, m_qi, m_qq) in Q14, None = the identity"""
+        d = None if dc is None else np.ascontiguousarray(dc, dtype=np.int32).reshape(2)
+        t = None if m is None else np.ascontiguousarray(m, dtype=np.int16).reshape(4)
+        self._call("set_correction", int(capture),
+                   None if d is None else d.ctypes.data_as(C.POINTER(C.c_int32)),
+                   None if t is None else t.ctypes.data_as(C.POINTER(C.c_int16)))
+
+    def correction(self, capture: int):
+        """(dc int32 [2], m int16 [4]) of one capture"""
+        dc, m = np.zeros(2, dtype=np.int32), np.zeros(4, dtype=np.int16)
+        self._call("get_correction", int(capture), dc.ctypes.data_as(C.POINTER(C.c_int32)),
+                   m.ctypes.data_as(C.POINTER(C.c_int16)))
+        return dc, m
+
+    def process(self, captures: np.ndarray, want_out: bool = True, want_moments: bool = True):
+        """captures int8 [n_captures, n_bytes] -> (out int8 [n_captures, n_bytes] or None, moments int64 [n_captures, 8]
+        or None); blocking"""
+        cap = np.ascontiguousarray(captures, dtype=np.int8).reshape(self.W, -1)
+        out = np.zeros_like(cap) if want_out else None
+        mom = np.zeros((self.W, 8), dtype=np.int64) if want_moments else None
+        self._call("process", _ptr(cap), cap.shape[1], _ptr(out), _ptr(mom))
+        return out, mom
+
+    def process_device(self, d_in, in_stride: int, n_bytes: int, d_out, out_stride: int, d_moments=None, stream=None):
+        """device pointers (ints), d_out or d_moments may be None; asynchronous on stream (None = the handle's own)"""
+        self._call("process_device", _ptr(d_in), int(in_stride), int(n_bytes), _ptr(d_out), int(out_stride),
+                   _ptr(d_moments), _ptr(stream))
+
+    def debug_set_workgroups(self, n: int):
+        """test hook (HRFD_DEBUG_HOOKS=1): the workgroups a launch aims for, 2048 by default; 1 gives every capture one"""
+        self._call("debug_set_workgroups", int(n))
 
 
 class Engine:

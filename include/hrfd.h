@@ -517,6 +517,63 @@ int hrfd_spec_process_device(hrfd_spec *s, const int8_t *d_captures, uint64_t ca
                              uint64_t *d_power, uint64_t *d_band_power, uint8_t *d_present, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * Conditioner bank: W wideband captures -> the same captures with the radio's DC offset and IQ imbalance taken out, and
+ * the moments a correction is solved from (no reference counterpart: the reference tunes every radio 64 kHz off its
+ * station, Radio.cc:1191, and hears one narrow channel, so neither the DC spur nor a station's image reaches it; a
+ * wideband capture has both in the band hrfd_spec_* surveys).  A capture is int8 IQ at any rate (the bank does not know
+ * R); a call takes n_bytes (even, 2 .. 2^30) from every capture and is a pure function of those bytes and the handle's
+ * correction records: no history, no counter, nothing carried to the next call.  Exact integer arithmetic, the same on
+ * every device (tests/cal_model.py restates it); shifts are arithmetic:
+ *   record    per capture: dc_i, dc_q int32 in Q8 (1/256 LSB), |dc| <= 32512; m_ii, m_iq, m_qi, m_qq int16 in Q14.
+ *             Default: identity, dc = 0, m = (16384, 0, 0, 16384).  The setter refuses a row with |m_a| + |m_b| > 32768
+ *             (rows (m_ii, m_iq) and (m_qi, m_qq)): with |x| <= 32768 + 32512 = 65280 the int32 sums below then cannot
+ *             overflow, 32768 x 65280 + 2^21 < 2^31.
+ *   apply     xi = (I << 8) - dc_i, xq = (Q << 8) - dc_q
+ *             yi = (m_ii xi + m_iq xq + 2^21) >> 22, yq = (m_qi xi + m_qq xq + 2^21) >> 22; the output is sat8(y).
+ *             The identity record returns the input byte for byte (-128 included).  Any matrix inside the row rule is
+ *             allowed: the same call injects an imbalance as well as it removes one.
+ *   moments   per capture and call eight 64-bit words {n, S_I, S_Q, S_II, S_QQ, S_IQ, clips, 0}: n = n_bytes / 2 and the
+ *             sums of I, Q, I^2, Q^2, I Q over the call's RAW INPUT samples (int64, two's complement), clips = the number
+ *             of output components (I and Q counted apart) outside -128..127 before sat8, 0 when no output is asked for.
+ *             The words of calls add: summing them over about a second, and forgetting old ones, is the caller's policy.
+ *   solver    hrfd_cal_solve, host only, no device: IEEE double, only + - x / and sqrt, no fused multiply-add, in this
+ *             order (every line one rounding per operation, left to right):
+ *               n = (double)moments[0]; mi = S_I / n; mq = S_Q / n
+ *               vii = S_II / n - mi mi; vqq = S_QQ / n - mq mq; viq = S_IQ / n - mi mq; D = vii vqq - viq viq
+ *               dc = floor(mean 256 + 0.5) clamped to +-32512
+ *               r = sqrt(D); m = (16384, 0, floor(((-viq) / r) 16384 + 0.5), floor((vii / r) 16384 + 0.5))
+ *             Gram-Schmidt with I as the reference: the corrected capture has equal variances on both rails and no I/Q
+ *             correlation.  If n <= 0 (then dc = 0 too), or not vii > 0, or not D > 0, or the row (m_qi, m_qq) breaks the
+ *             row rule or leaves int16, m is the identity, dc is kept, and the return value is HRFD_CAL_DEGENERATE (1, not
+ *             an error); else HRFD_OK.  Assumption: the capture's content is circular (E[z^2] = 0), which a band of
+ *             stations is and one real-valued test tone is not: a capture that holds little but such a tone stays at the
+ *             identity.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well); setters never wait for the
+ * device: the records a setter changed are copied to the device on the next call's stream, ahead of its launch.  Calls may
+ * use different streams: each launch is ordered on the device behind the handle's previous one.
+ *   hrfd_cal_set_correction   capture: an index or HRFD_ALL_CHANNELS (every capture); dc NULL = (0, 0), m NULL = identity
+ *   hrfd_cal_process          host buffers: captures [W][n_bytes] -> out [W][n_bytes] and / or moments [W][8]; either may
+ *                             be NULL, not both; blocking
+ *   hrfd_cal_process_device   device buffers, rows in_stride / out_stride bytes apart, any byte address and any stride
+ *                             >= n_bytes; d_out == d_in with equal strides is allowed (the operation is element-wise), any
+ *                             other overlap of the two is refused; d_moments [W][8] 8-byte aligned; d_out or d_moments
+ *                             may be NULL, not both; asynchronous on `stream` (a hipStream_t, NULL = the handle's own)
+ */
+typedef struct hrfd_cal hrfd_cal;
+#define HRFD_CAL_MAX_BYTES (1u << 30)
+#define HRFD_CAL_MAX_DC 32512
+#define HRFD_CAL_MAX_ROW 32768
+#define HRFD_CAL_DEGENERATE 1
+int hrfd_cal_create(uint32_t n_captures, int device, hrfd_cal **out);
+int hrfd_cal_destroy(hrfd_cal *c);
+int hrfd_cal_set_correction(hrfd_cal *c, uint32_t capture, const int32_t dc[2], const int16_t m[4]);
+int hrfd_cal_get_correction(hrfd_cal *c, uint32_t capture, int32_t dc[2], int16_t m[4]);
+int hrfd_cal_process(hrfd_cal *c, const int8_t *captures, uint32_t n_bytes, int8_t *out, int64_t *moments);
+int hrfd_cal_process_device(hrfd_cal *c, const int8_t *d_in, uint64_t in_stride, uint32_t n_bytes, int8_t *d_out,
+                            uint64_t out_stride, int64_t *d_moments, void *stream);
+int hrfd_cal_solve(const int64_t moments[8], int32_t dc[2], int16_t m[4]);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",
