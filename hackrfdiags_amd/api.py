@@ -43,8 +43,11 @@ class Rx:
         check(self.L.hrfd_rx_create(self.n, device, C.byref(h)), "hrfd_rx_create")
         self.h = h
         self.gain_db = 0
+        self._transports = []          # Ingest objects over this handle: destroyed before it (they use it when they go)
 
     def close(self):
+        for t in list(getattr(self, "_transports", ())):
+            t.close()
         if getattr(self, "h", None):
             self.L.hrfd_rx_destroy(self.h)
             self.h = None
@@ -287,11 +290,14 @@ class Ingest:
         check(self.L.hrfd_ingest_create(rx.h, self.block_bytes, self.n_blocks, int(n_slots), C.byref(h)),
               "hrfd_ingest_create")
         self.h = h
+        rx._transports.append(self)    # whichever of the two goes first, the transport is destroyed before the handle
 
     def close(self):
         if getattr(self, "h", None):
             self.L.hrfd_ingest_destroy(self.h)
             self.h = None
+            if self in self.rx._transports:
+                self.rx._transports.remove(self)
 
     __del__ = close
 
@@ -367,6 +373,20 @@ class Fanout:
     def scatter(self, src_device: int, d_iq_all, block_bytes: int, n_blocks: int, src_stream=None):
         check(self.L.hrfd_fanout_scatter(self.h, int(src_device), _ptr(d_iq_all), int(block_bytes), int(n_blocks),
                                          _ptr(src_stream)), "hrfd_fanout_scatter")
+
+    def shards(self) -> int:
+        n = C.c_uint32(0)
+        check(self.L.hrfd_fanout_shards(self.h, C.byref(n)), "hrfd_fanout_shards")
+        return int(n.value)
+
+    def input(self, shard: int, block_bytes: int, n_blocks: int):
+        """instead of scatter, for a host that feeds every device itself: (device address of the shard's input buffer
+        [count][n_blocks][block_bytes], first channel, count).  Size every shard's buffer with the same block_bytes and
+        n_blocks before filling any: a call that grows the buffers moves them"""
+        p, first, count = C.c_void_p(), C.c_uint32(0), C.c_uint32(0)
+        check(self.L.hrfd_fanout_input(self.h, int(shard), int(block_bytes), int(n_blocks), C.byref(p), C.byref(first),
+                                       C.byref(count)), "hrfd_fanout_input")
+        return int(p.value), int(first.value), int(count.value)
 
     def process(self, gain_db: int = 0):
         check(self.L.hrfd_fanout_process(self.h, int(gain_db)), "hrfd_fanout_process")

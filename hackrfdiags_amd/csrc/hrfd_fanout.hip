@@ -16,6 +16,10 @@
 //   hrfd_fanout_process   every shard demodulates its buffer (asynchronous, all devices at once)
 //   hrfd_fanout_collect   per shard: wait, replay what failed its speculation exactly, PCM / n_pcm to the destination
 //
+// One batch at a time: from a successful process until its collect the batch is IN FLIGHT, and scatter, input and process
+// answer HRFD_ESTATE without touching it -- collect replays failed channels from the shards' input buffers with the
+// batch's block size and gain_db, which a second scatter or process would have replaced.
+//
 // Several shards may name the same device (a one-GPU box rehearses the whole path that way: the tests do).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -247,6 +251,10 @@ extern "C" int hrfd_fanout_scatter(hrfd_fanout *f, int src_device, const int8_t 
   {
     return fail(HRFD_EINVAL, "hrfd_fanout_scatter: NULL");
   }
+  if (f->in_flight)
+  {
+    return fail(HRFD_ESTATE, "hrfd_fanout_scatter: a batch is in flight (collect it first)");
+  }
   int rc = fanout_buffers(f, block_bytes, n_blocks);
   if (rc != HRFD_OK)
   {
@@ -301,6 +309,10 @@ extern "C" int hrfd_fanout_input(hrfd_fanout *f, uint32_t shard, uint32_t block_
   {
     return fail(HRFD_EINVAL, "hrfd_fanout_input: bad handle or shard");
   }
+  if (f->in_flight)
+  {
+    return fail(HRFD_ESTATE, "hrfd_fanout_input: a batch is in flight (collect it first)");
+  }
   const int rc = fanout_buffers(f, block_bytes, n_blocks);
   if (rc != HRFD_OK)
   {
@@ -318,9 +330,17 @@ extern "C" int hrfd_fanout_input(hrfd_fanout *f, uint32_t shard, uint32_t block_
 // from the shards' input buffers: asynchronous, every device at once.
 extern "C" int hrfd_fanout_process(hrfd_fanout *f, uint32_t gain_db)
 {
-  if (f == nullptr || f->n_blocks == 0)
+  if (f == nullptr)
+  {
+    return fail(HRFD_EINVAL, "hrfd_fanout_process: NULL");
+  }
+  if (f->n_blocks == 0)
   {
     return fail(HRFD_ESTATE, "hrfd_fanout_process: nothing scattered yet");
+  }
+  if (f->in_flight)
+  {
+    return fail(HRFD_ESTATE, "hrfd_fanout_process: a batch is in flight (collect it first)");
   }
   for (hrfd_fanout::Shard &s : f->shards)
   {
@@ -345,9 +365,13 @@ extern "C" int hrfd_fanout_process(hrfd_fanout *f, uint32_t gain_db)
 extern "C" int hrfd_fanout_collect(hrfd_fanout *f, int dst_device, int16_t *d_pcm_all, uint32_t *d_n_pcm_all,
                                    uint32_t *n_replayed)
 {
-  if (f == nullptr || !f->in_flight || d_pcm_all == nullptr)
+  if (f == nullptr || d_pcm_all == nullptr)
   {
-    return fail(HRFD_ESTATE, "hrfd_fanout_collect: no batch in flight, or no destination");
+    return fail(HRFD_EINVAL, "hrfd_fanout_collect: NULL handle or destination");
+  }
+  if (!f->in_flight)
+  {
+    return fail(HRFD_ESTATE, "hrfd_fanout_collect: no batch in flight");
   }
   const uint32_t npcm = (f->block_bytes + 511u) / 512u;
   uint32_t replayed = 0;

@@ -136,7 +136,21 @@ extern "C" int hrfd_ingest_create(hrfd_rx *rx, uint32_t block_bytes, uint32_t n_
   return HRFD_OK;
 }
 
-extern "C" int hrfd_ingest_destroy(hrfd_ingest *g) { return ingest_free(g); }
+// Leaves the rx handle where a sequential caller stands after every SUBMITTED batch: the batches still in flight are
+// collected first, so channels that failed in them are replayed like in any collect (their results go nowhere) and no
+// channel stays poisoned -- without this the clean channels of an uncollected failed batch had advanced, the failed ones
+// had not, and the next launch on the handle would not commit them.
+extern "C" int hrfd_ingest_destroy(hrfd_ingest *g)
+{
+  while (g != nullptr && g->in_flight != 0)
+  {
+    if (hrfd_ingest_collect(g, nullptr, nullptr, nullptr, nullptr) != HRFD_OK)
+    {
+      break;                                         // (a device error: nothing more can be repaired, the buffers still go)
+    }
+  }
+  return ingest_free(g);
+}
 
 // The next free slot's pinned input buffer, [n_channels][n_blocks][block_bytes].  HRFD_ESTATE
 // when every slot is submitted or still held by the consumer (collect first).

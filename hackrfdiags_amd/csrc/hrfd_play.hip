@@ -75,10 +75,43 @@ struct hrfd_play
   uint8_t *d_ring = nullptr;
   uint32_t length = 0;                 // 0: nothing loaded
   std::vector<uint32_t> index;         // host mirror of the read positions
-  uint32_t *d_index = nullptr;
+  // The positions a launch reads, one buffer per launch that may still be pending: hrfd_play_get_device takes any caller
+  // stream, so the kernel of one call can be waiting on its stream while the next call (another stream) hands over the
+  // positions behind it.  `done` is recorded behind the kernel; a buffer is taken again once its event has passed.
+  struct IndexBuf
+  {
+    uint32_t *d_index = nullptr;
+    hipEvent_t done = nullptr;
+  };
+  std::vector<IndexBuf> index_bufs;
   int8_t *d_out = nullptr;             // staging of hrfd_play_get
   size_t cap_out = 0;
 };
+
+// One more positions buffer with its event (the device is current).
+static hipError_t play_index_buf(hrfd_play *h, hrfd_play::IndexBuf **out)
+{
+  hrfd_play::IndexBuf b;
+  hipError_t e = hipMalloc((void **)&b.d_index, sizeof(uint32_t) * h->n_channels);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&b.done, hipEventDisableTiming);
+  if (e != hipSuccess)
+  {
+    if (b.d_index) (void)hipFree(b.d_index);
+    return e;
+  }
+  h->index_bufs.push_back(b);
+  if (out != nullptr) *out = &h->index_bufs.back();
+  return hipSuccess;
+}
+
+// Waits for every kernel the handle has launched, on whichever stream (the device is current).
+static void play_wait_launched(hrfd_play *h)
+{
+  for (hrfd_play::IndexBuf &b : h->index_bufs)
+  {
+    (void)hipEventSynchronize(b.done);
+  }
+}
 
 extern "C" int hrfd_play_create(uint32_t n_channels, int device, hrfd_play **out)
 {
@@ -103,7 +136,7 @@ extern "C" int hrfd_play_create(uint32_t n_channels, int device, hrfd_play **out
   h->n_channels = n_channels;
   h->index.assign(n_channels, 0u);
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc((void **)&h->d_index, sizeof(uint32_t) * n_channels);
+  if (e == hipSuccess) e = play_index_buf(h, nullptr);
   if (e != hipSuccess)
   {
     rc = fail(HRFD_ENOMEM, "hrfd_play_create: %s", hipGetErrorString(e));
@@ -122,15 +155,21 @@ extern "C" int hrfd_play_destroy(hrfd_play *h)
   }
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  play_wait_launched(h);
   if (h->d_ring) (void)hipFree(h->d_ring);
-  if (h->d_index) (void)hipFree(h->d_index);
+  for (hrfd_play::IndexBuf &b : h->index_bufs)
+  {
+    (void)hipFree(b.d_index);
+    (void)hipEventDestroy(b.done);
+  }
   if (h->d_out) (void)hipFree(h->d_out);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return HRFD_OK;
 }
 
-// DataProvider::loadIqFile (:235-300): a new image replaces the old one, every position restarts at 0
+// DataProvider::loadIqFile (:235-300): a new image replaces the old one, every position restarts at 0.  Waits for every
+// hrfd_play_get_device launched so far, on the caller's streams too: the old image is freed here.
 extern "C" int hrfd_play_load(hrfd_play *h, const int8_t *bytes, uint32_t n_bytes)
 {
   using namespace hrfd;
@@ -140,6 +179,7 @@ extern "C" int hrfd_play_load(hrfd_play *h, const int8_t *bytes, uint32_t n_byte
   }
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipStreamSynchronize(h->stream));
+  play_wait_launched(h);
   if (h->d_ring)
   {
     (void)hipFree(h->d_ring);
@@ -231,12 +271,31 @@ extern "C" int hrfd_play_get_device(hrfd_play *h, int8_t *d_out, uint64_t channe
   }
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = (stream != nullptr) ? (hipStream_t)stream : h->stream;
-  HIP_TRY(hipMemcpyAsync(h->d_index, h->index.data(), sizeof(uint32_t) * h->n_channels, hipMemcpyHostToDevice, s));
+  // a positions buffer that no pending kernel reads (an event that was never recorded counts as passed)
+  hrfd_play::IndexBuf *ib = nullptr;
+  for (hrfd_play::IndexBuf &b : h->index_bufs)
+  {
+    if (hipEventQuery(b.done) == hipSuccess)
+    {
+      ib = &b;
+      break;
+    }
+  }
+  (void)hipGetLastError();                                 // (hipErrorNotReady of a query is no error of this call)
+  if (ib == nullptr)
+  {
+    const hipError_t e = play_index_buf(h, &ib);
+    if (e != hipSuccess)
+    {
+      return fail(HRFD_ENOMEM, "hrfd_play_get_device: %s", hipGetErrorString(e));
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(ib->d_index, h->index.data(), sizeof(uint32_t) * h->n_channels, hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));                        // the host vector changes below
   PlayParams Q;
   Q.ring = h->d_ring;
   Q.length = h->length;
-  Q.index = h->d_index;
+  Q.index = ib->d_index;
   Q.out = d_out;
   Q.ch_stride = channel_stride;
   Q.bytes = bytes_per_channel;
@@ -244,6 +303,7 @@ extern "C" int hrfd_play_get_device(hrfd_play *h, int8_t *d_out, uint64_t channe
   const uint64_t threads = (uint64_t)((bytes_per_channel + 15u) / 16u) * h->n_channels;
   hipLaunchKernelGGL(k_play, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s, Q);
   HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ib->done, s));
   for (uint32_t c = 0; c < h->n_channels; c++)
   {
     h->index[c] = (uint32_t)(((uint64_t)h->index[c] + bytes_per_channel) % h->length);

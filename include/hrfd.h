@@ -199,8 +199,12 @@ uint32_t hrfd_demod_pcm_capacity(uint32_t bytes_per_channel);   /* ceil(bytes_pe
  *              none is free) -> fill -> hrfd_ingest_submit (returns at once)
  *   consumer:  hrfd_ingest_collect (oldest submitted batch; blocks; pcm [C][B][hrfd_rx_pcm_capacity(block_bytes)],
  *              n_pcm / magnitude / signal_allowed [C][B]; pointers valid until that slot is
- *              acquired again)
+ *              acquired again; any of the four out pointers may be NULL)
  * The rx handle must not be used by other calls while batches are in flight.
+ * hrfd_ingest_destroy with batches still in flight collects them first: afterwards the rx handle is in the state a
+ * sequential caller reaches after every SUBMITTED batch -- channels that failed in an uncollected batch are replayed
+ * (their results are discarded), no channel is left marked as failed, and the stream may go on with any hrfd_rx_* call.
+ * A slot that was acquired and never submitted is not a batch.  Destroy the transport before its rx handle.
  */
 typedef struct hrfd_ingest hrfd_ingest;
 int hrfd_ingest_create(hrfd_rx *rx, uint32_t block_bytes, uint32_t n_blocks, uint32_t n_slots,
@@ -229,6 +233,11 @@ int hrfd_ingest_replayed(hrfd_ingest *g, uint64_t *n_batches);
  *   hrfd_fanout_collect   waits, replays exactly what failed its speculation (as hrfd_rx_process_block does), gathers
  *                         pcm [n_channels][n_blocks][hrfd_rx_pcm_capacity(block_bytes)] and n_pcm [n_channels][n_blocks] (may be NULL)
  *                         into buffers on dst_device; *n_replayed (may be NULL) = channels replayed
+ * One batch at a time: from a successful hrfd_fanout_process until its hrfd_fanout_collect the batch is IN FLIGHT, and
+ * hrfd_fanout_scatter, hrfd_fanout_input and hrfd_fanout_process answer HRFD_ESTATE and leave it untouched (collect
+ * replays failed channels from the shards' input buffers with the batch's block size and gain_db; a second scatter or
+ * process would replace them).  hrfd_fanout_collect without a batch in flight and hrfd_fanout_process before any
+ * scatter / input are HRFD_ESTATE too; a NULL handle or destination is HRFD_EINVAL.
  * The setters take channel numbers of the whole bank (HRFD_ALL_CHANNELS: every shard).
  * (The multi-process counterpart -- one rank per GPU, RCCL -- is hackrfdiags_amd/shard.py, used by bench.py --gpus N.)
  */
@@ -323,6 +332,12 @@ int hrfd_txring_stats(hrfd_txring *r, uint32_t channel, uint32_t *out6);
  * (SURVEY 8f rank 4).  hrfd_play_get_device fills d_out[c][bytes_per_channel] (channel_stride bytes
  * apart) from every channel's position and advances it modulo the file length, exactly like
  * retrieveIqDataFromBuffer; nothing is written while no file is loaded (as in the reference).
+ * Streams: hrfd_play_get_device is asynchronous on the caller's stream (NULL: the handle's own).  Every call hands its
+ * kernel the positions of THAT call in a buffer of its own, so calls on different streams may follow each other while
+ * earlier kernels are still pending; the positions hrfd_play_get_position reports advance at the call, in call order.
+ * hrfd_play_load (and load_file, destroy) free the image: they wait, by themselves, for every kernel that
+ * hrfd_play_get_device has launched so far, on whichever stream -- the caller need not synchronise first, but must not
+ * call them concurrently with hrfd_play_get_device from another thread (a handle is not thread-safe).
  */
 typedef struct hrfd_play hrfd_play;
 int hrfd_play_create(uint32_t n_channels, int device, hrfd_play **out);

@@ -42,6 +42,9 @@ GROUPS = [
     ("squelch_sweep", "test_gpu_squelch_sweep", "", 40),
     ("sincos_every_float", "test_gpu_sincos", "", 8),
     ("nco_sweep", "test_gpu_nco_sweep", "", 11),
+    ("ingest_edges", "test_gpu_ingest_edges", "", 30),
+    ("fanout_edges", "test_gpu_fanout_edges", "", 7),
+    ("play_edges", "test_gpu_play_edges", "", 7),
 ]
 
 
