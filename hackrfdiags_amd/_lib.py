@@ -213,6 +213,16 @@ def load() -> C.CDLL:
         L.hrfd_cal_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp]
         L.hrfd_cal_solve.argtypes = [_i64p, _i32p, _i16p]
         L.hrfd_cal_debug_set_workgroups.argtypes = [_vp, C.c_int]
+    if hasattr(L, "hrfd_tone_create"):                     # (an older build named by HRFD_LIB has no tone bank)
+        _u8p = C.POINTER(C.c_uint8)
+        L.hrfd_tone_create.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_tone_destroy.argtypes = [_vp]
+        L.hrfd_tone_set_tones.argtypes = [_vp, _u32p, _u8p, C.c_uint32]
+        L.hrfd_tone_n_tones.argtypes = [_vp, _u32p]
+        L.hrfd_tone_set_window.argtypes = [_vp, _i16p]
+        L.hrfd_tone_set_threshold.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint64]
+        L.hrfd_tone_process.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]
+        L.hrfd_tone_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

@@ -545,7 +545,7 @@ def ddc_step(offset_hz: float, decimation: int) -> int:
 
 
 class _Bank:
-    """What Ddc, Duc, Spectrum and Conditioner share: the handle of hrfd_<_prefix>_create and its release."""
+    """What Ddc, Duc, Spectrum, Conditioner and Tones share: the handle of hrfd_<_prefix>_create and its release."""
     _prefix = ""
 
     def _create(self, *args):
@@ -895,6 +895,133 @@ class Conditioner(_Bank):
     def debug_set_workgroups(self, n: int):
         """test hook (HRFD_DEBUG_HOOKS=1): the workgroups a launch aims for, 2048 by default; 1 gives every capture one"""
         self._call("debug_set_workgroups", int(n))
+
+
+TONE_FS = 8000
+TONE_GROUPS = 4
+TONE_MAX_TONES = 128
+TONE_MAX_RATIO = 1 << 20
+TONE_NO_BEST = 255
+# the 50 CTCSS sub-tones (TIA-603 and the common extensions)
+CTCSS_HZ = (67.0, 69.3, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9, 114.8, 118.8,
+            123.0, 127.3, 131.8, 136.5, 141.3, 146.2, 151.4, 156.7, 159.8, 162.2, 165.5, 167.9, 171.3, 173.8, 177.3, 179.9,
+            183.5, 186.2, 189.9, 192.8, 196.6, 199.5, 203.5, 206.5, 210.7, 218.1, 225.7, 229.1, 233.6, 241.8, 250.3, 254.1)
+DTMF_LOW_HZ = (697.0, 770.0, 852.0, 941.0)
+DTMF_HIGH_HZ = (1209.0, 1336.0, 1477.0, 1633.0)
+DTMF_KEYS = ("123A", "456B", "789C", "*0#D")
+
+
+def tone_step(f_hz: float) -> int:
+    """the tone bank's phase step for a tone at f_hz in 8 kS/s audio: round(f / 8000 * 2^32) mod 2^32"""
+    return int(round(float(f_hz) / TONE_FS * 2.0 ** 32)) & 0xFFFFFFFF
+
+
+def tone_default_window(frame_len: int) -> np.ndarray:
+    """the bank's default window: round(32767 * 0.5 * (1 - cos(2 pi n / L)))"""
+    n = np.arange(int(frame_len), dtype=np.float64)
+    return np.floor(32767.0 * 0.5 * (1.0 - np.cos(2.0 * np.pi * n / int(frame_len))) + 0.5).astype(np.int16)
+
+
+def tone_gain(window) -> float:
+    """P / E of a pure tone on a tone's frequency under the window: S1^2 / (2 S2), S1 = sum w / 32768, S2 = sum (w / 32768)^2"""
+    w = np.asarray(window, dtype=np.float64) / 32768.0
+    return float(w.sum() ** 2 / (2.0 * (w * w).sum()))
+
+
+def tone_threshold(window, fraction: float) -> int:
+    """set_threshold's ratio_q8 for "the tone holds at least this fraction of the frame's energy" under the window"""
+    return min(max(int(round(256.0 * float(fraction) * tone_gain(window))), 0), TONE_MAX_RATIO)
+
+
+def tone_fraction(power, energy, window) -> np.ndarray:
+    """the fraction of each frame's energy a tone holds: power [..., K] / (energy [...] x tone_gain), 0 for an empty frame"""
+    p = np.asarray(power, dtype=np.float64)
+    e = np.asarray(energy, dtype=np.float64)[..., None] * tone_gain(window)
+    return np.where(e > 0, p / np.maximum(e, 1e-300), 0.0)
+
+
+def dtmf_digit(low_best: int, high_best: int) -> str:
+    """the key of a row (index into DTMF_LOW_HZ) and a column (index into DTMF_HIGH_HZ)"""
+    return DTMF_KEYS[int(low_best)][int(high_best)]
+
+
+class Tones(_Bank):
+    """A bank of tone detectors (hrfd_tone_*): the PCM of n_channels channels as Rx / Ddc.receive write it in, per frame of
+    frame_len samples the power at every tone of one shared list, the frame's energy and a verdict per tone group out."""
+
+    _prefix = "tone"
+
+    def __init__(self, n_channels: int, frame_len: int, device: int = -1):
+        self.n, self.frame_len = int(n_channels), int(frame_len)
+        self._create(self.n, self.frame_len, device)
+        self.window = tone_default_window(self.frame_len)
+
+    def set_tones(self, freqs_hz=None, groups=None, steps=None):
+        """the whole list: frequencies in Hz (tone_step) or raw steps; groups 0..3 per tone, None = all 0"""
+        if (freqs_hz is None) == (steps is None):
+            raise ValueError("set_tones takes either freqs_hz or steps")
+        s = np.ascontiguousarray([tone_step(f) for f in freqs_hz] if steps is None else
+                                 [int(v) & 0xFFFFFFFF for v in steps], dtype=np.uint32)
+        g = None if groups is None else np.ascontiguousarray(groups, dtype=np.uint8)
+        if g is not None and g.size != s.size:
+            raise ValueError(f"{s.size} tones but {g.size} groups")
+        self._call("set_tones", s.ctypes.data_as(C.POINTER(C.c_uint32)),
+                   None if g is None else g.ctypes.data_as(C.POINTER(C.c_uint8)), s.size)
+
+    @property
+    def n_tones(self) -> int:
+        v = C.c_uint32(0)
+        self._call("n_tones", C.byref(v))
+        return int(v.value)
+
+    def set_window(self, w=None):
+        """frame_len int16 values in -32767..32767; None restores the default (Hann)"""
+        if w is None:
+            self._call("set_window", None)
+            self.window = tone_default_window(self.frame_len)
+            return
+        t = np.ascontiguousarray(w, dtype=np.int16)
+        if t.size != self.frame_len:
+            raise ValueError(f"the window needs {self.frame_len} entries, got {t.size}")
+        self._call("set_window", t.ctypes.data_as(C.POINTER(C.c_int16)))
+        self.window = t.copy()
+
+    def set_threshold(self, group=ALL, fraction=None, ratio_q8=None, min_energy=None):
+        """present needs P_best >= (E ratio_q8) >> 8 and E >= min_energy: ratio_q8 directly, or the fraction of the frame's
+        energy under the window set last (tone_threshold); defaults 16 L and 256 L"""
+        if fraction is not None and ratio_q8 is not None:
+            raise ValueError("set_threshold takes either fraction or ratio_q8")
+        r = tone_threshold(self.window, fraction) if fraction is not None else \
+            16 * self.frame_len if ratio_q8 is None else int(ratio_q8)
+        e = 256 * self.frame_len if min_energy is None else int(min_energy)
+        self._call("set_threshold", int(group), r, e)
+
+    def _frames(self, n_blocks: int) -> int:
+        return 512 * int(n_blocks) // self.frame_len
+
+    def process(self, pcm: np.ndarray, n_pcm=None):
+        """pcm int16 [n_channels, n_blocks, 512], n_pcm uint32 [n_channels, n_blocks] or None -> (power uint64 [C, F, K],
+        energy uint64 [C, F], valid uint32 [C, F], best uint8 [C, F, 4], present uint8 [C, F, 4]); blocking"""
+        x = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.n, -1)
+        n_blocks = x.shape[1] // 512
+        if x.shape[1] != 512 * n_blocks:
+            raise ValueError(f"a channel's PCM must be whole blocks of 512 samples, got {x.shape[1]} samples")
+        npc = None if n_pcm is None else np.ascontiguousarray(n_pcm, dtype=np.uint32).reshape(self.n, n_blocks)
+        F, K = self._frames(n_blocks), self.n_tones
+        power = np.zeros((self.n, F, K), dtype=np.uint64)
+        energy = np.zeros((self.n, F), dtype=np.uint64)
+        valid = np.zeros((self.n, F), dtype=np.uint32)
+        best = np.zeros((self.n, F, TONE_GROUPS), dtype=np.uint8)
+        present = np.zeros((self.n, F, TONE_GROUPS), dtype=np.uint8)
+        self._call("process", _ptr(x), _ptr(npc), n_blocks, _ptr(power), _ptr(energy), _ptr(valid), _ptr(best), _ptr(present))
+        return power, energy, valid, best, present
+
+    def process_device(self, d_pcm, channel_stride: int, d_n_pcm, n_blocks: int, d_power=None, d_energy=None, d_valid=None,
+                       d_best=None, d_present=None, stream=None):
+        """device pointers (ints), d_n_pcm and any output may be None (not every output); asynchronous on stream (None = the
+        handle's own)"""
+        self._call("process_device", _ptr(d_pcm), int(channel_stride), _ptr(d_n_pcm), int(n_blocks), _ptr(d_power),
+                   _ptr(d_energy), _ptr(d_valid), _ptr(d_best), _ptr(d_present), _ptr(stream))
 
 
 class Engine:

@@ -589,6 +589,67 @@ int hrfd_cal_process_device(hrfd_cal *c, const int8_t *d_in, uint64_t in_stride,
 int hrfd_cal_solve(const int64_t moments[8], int32_t dc[2], int16_t m[4]);
 
 /* ------------------------------------------------------------------------------
+ * Tone bank: the PCM of C channels -> per frame the power at K tone frequencies, the frame's energy and a verdict per
+ * tone group: which CTCSS sub-tone, which DTMF row and column, whether a pilot is there (no reference counterpart: the
+ * reference plays its one channel to a listener; nobody listens to a thousand).  It reads what hrfd_rx_process_device /
+ * hrfd_ddc_receive write: PCM rows [C][n_blocks][512] int16 at 8 kS/s and, optionally, n_pcm [C][n_blocks].  A call is a
+ * pure function of its input and the handle's settings: no history, no counter, the phase is frame-local.  Exact integer
+ * arithmetic, the same on every device (tests/tone_model.py restates it); shifts are arithmetic:
+ *   sizes     C = 1..65536 channels; frame length L = 128, 256, .., 8192 (16 ms .. 1.024 s), fixed at create; K = 1..128
+ *             tones, one list for every channel; HRFD_TONE_GROUPS = 4 groups; n_blocks = 1..1024 with 512 n_blocks a
+ *             multiple of L; F = 512 n_blocks / L frames per channel, back to back without overlap: sample j of a channel
+ *             is sample j mod 512 of block j div 512, frame f holds samples f L .. f L + L - 1.
+ *   input     x[n] = the int16 sample, or 0 where n_pcm is given and the sample's position in its block is
+ *             >= min(n_pcm[c][b], 512): a squelched block (n_pcm = 0) and a short one; the bytes there do not matter.
+ *             valid[c][f] = the samples of the frame taken from the input (L when n_pcm is NULL).
+ *   window    u[n] = (x[n] w[n] + 2^14) >> 15; w: L int16 entries in -32767..32767 (-32768 is refused, so |u| <= 32767).
+ *             Default round(32767 * 0.5 * (1 - cos(2 pi n / L))), host, double: the spectrum bank's formula.
+ *   tone k    theta(n) = step_k n mod 2^32, n = 0..L-1 inside the frame; step = round(f / 8000 * 2^32) mod 2^32.  The
+ *             mixer indices are the DDC's: i = ((theta + 2^19) >> 20) & 4095, c = COS[i], s = COS[(i - 1024) & 4095], COS
+ *             the table behind hrfd_q15_table("DDC_COS").
+ *   sums      I_k = sum u[n] c_k[n], Q_k = sum u[n] s_k[n], exact in int64 (|.| < 2^43); I' = (I + 2^14) >> 15, Q' alike
+ *             (|.| <= 2^28); P_k = I'^2 + Q'^2 (uint64, < 2^57); E = sum u[n]^2 (uint64, < 2^43).
+ *   groups    every tone has a group 0..3 (say DTMF rows 0, DTMF columns 1, CTCSS 2).  Per frame and group: best = the
+ *             lowest index among the group's tones with the largest P, 255 for a group without tones (present = 0 then);
+ *             present = (valid == L) && (E >= E_min_g) && (P_best >= ((E T_g) >> 8)), T_g a uint32 in Q8, at most 2^20
+ *             (E T stays inside uint64), E_min_g <= 2^43.  A pure tone on the frequency gives P / E ~ S1^2 / (2 S2) with
+ *             S1 = sum w / 32768, S2 = sum (w / 32768)^2, so T says "the tone holds at least this fraction of the
+ *             frame's energy".  Defaults: T_g = 16 L (ratio L / 16: about 0.19 of the energy under the default window),
+ *             E_min_g = 256 L.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well); a call before any tones are set
+ * is refused.  Setters never wait for the device: what a setter changed is copied to the device on the next call's stream,
+ * ahead of its launch.  Calls may use different streams: each launch is ordered on the device behind the handle's previous
+ * one, so a call chains behind the receive call that filled its input when both are given the same stream.
+ *   hrfd_tone_set_tones       K steps and their groups (NULL: all 0); replaces the whole list
+ *   hrfd_tone_set_window      L entries; NULL restores the default
+ *   hrfd_tone_set_threshold   group: 0..3 or HRFD_ALL_CHANNELS (every group)
+ *   hrfd_tone_process         host buffers, dense: pcm [C][n_blocks][512], n_pcm [C][n_blocks] or NULL -> power [C][F][K],
+ *                             energy [C][F], valid [C][F], best [C][F][4], present [C][F][4]; any output may be NULL, not
+ *                             all; blocking
+ *   hrfd_tone_process_device  device buffers; channel rows channel_stride_bytes apart (even, >= 1024 n_blocks), d_pcm at
+ *                             any even address; d_n_pcm dense as hrfd_rx_* writes it, or NULL; d_power and d_energy 8-byte
+ *                             aligned, d_valid 4-byte aligned; asynchronous on `stream` (a hipStream_t, NULL = the handle's
+ *                             own)
+ */
+typedef struct hrfd_tone hrfd_tone;
+#define HRFD_TONE_GROUPS 4
+#define HRFD_TONE_MAX_TONES 128
+#define HRFD_TONE_MAX_BLOCKS 1024
+#define HRFD_TONE_MAX_RATIO (1u << 20)
+#define HRFD_TONE_MAX_ENERGY (1ull << 43)
+int hrfd_tone_create(uint32_t n_channels, uint32_t frame_len, int device, hrfd_tone **out);
+int hrfd_tone_destroy(hrfd_tone *t);
+int hrfd_tone_set_tones(hrfd_tone *t, const uint32_t *steps, const uint8_t *groups, uint32_t n_tones);
+int hrfd_tone_n_tones(hrfd_tone *t, uint32_t *n_tones);
+int hrfd_tone_set_window(hrfd_tone *t, const int16_t *w);
+int hrfd_tone_set_threshold(hrfd_tone *t, uint32_t group, uint32_t ratio_q8, uint64_t min_energy);
+int hrfd_tone_process(hrfd_tone *t, const int16_t *pcm, const uint32_t *n_pcm, uint32_t n_blocks, uint64_t *power,
+                      uint64_t *energy, uint32_t *valid, uint8_t *best, uint8_t *present);
+int hrfd_tone_process_device(hrfd_tone *t, const int16_t *d_pcm, uint64_t channel_stride_bytes, const uint32_t *d_n_pcm,
+                             uint32_t n_blocks, uint64_t *d_power, uint64_t *d_energy, uint32_t *d_valid, uint8_t *d_best,
+                             uint8_t *d_present, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",
