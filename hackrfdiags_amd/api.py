@@ -1024,6 +1024,110 @@ class Tones(_Bank):
                    _ptr(d_energy), _ptr(d_valid), _ptr(d_best), _ptr(d_present), _ptr(stream))
 
 
+AUDIO_MAX_BUSES = 64
+AUDIO_MAX_TAPS = 512
+AUDIO_MAX_LIST = 4096
+AUDIO_ANY_TONE = 254
+AUDIO_NO_TONE = 255
+AUDIO_UNITY_GAIN = 4096            # a bus gain of 1.0 (Q12)
+
+
+def audio_highpass_taps(T: int = 511, cutoff_hz: float = 300.0) -> np.ndarray:
+    """T odd int16 taps in Q14 for Audio.set_taps that take the sub-audible tones out of the voice band: a sinc low-pass at
+    cutoff_hz under np.blackman, normalised to unity at DC, subtracted from a unit impulse at the centre (spectral
+    inversion), round(h * 16384).  A design aid on the host, not part of the bank's exact contract."""
+    T = int(T)
+    if T < 3 or T > AUDIO_MAX_TAPS or T % 2 == 0:
+        raise ValueError(f"spectral inversion needs an odd tap count in 3..{AUDIO_MAX_TAPS - 1}, got {T}")
+    n = np.arange(T, dtype=np.float64) - (T - 1) / 2
+    low = np.sinc(2.0 * float(cutoff_hz) / TONE_FS * n) * np.blackman(T)
+    low /= low.sum()
+    h = -low
+    h[(T - 1) // 2] += 1.0
+    return np.floor(h * 16384.0 + 0.5).astype(np.int16)
+
+
+class Audio(_Bank):
+    """The audio bank (hrfd_audio_*): the PCM of n_channels channels as Rx / Ddc.receive write it in; every channel's audio
+    behind one voice filter and a click-free per-block gate, and n_buses monitor mixes of it out.  gate / gate_device turn
+    the verdicts of Tones into the gate (tone squelch)."""
+
+    _prefix = "audio"
+
+    def __init__(self, n_channels: int, n_buses: int = 1, device: int = -1):
+        self.n, self.m = int(n_channels), int(n_buses)
+        self._create(self.n, self.m, device)
+
+    def set_taps(self, taps):
+        """1..512 int16 taps in Q14 with sum |h| <= 65535, one list for every channel; zeroes every channel's history and
+        gate"""
+        t = np.ascontiguousarray(taps, dtype=np.int16).ravel()
+        self._call("set_taps", t.ctypes.data_as(C.POINTER(C.c_int16)), t.size)
+
+    def set_bus(self, bus: int, channels=(), gains=()):
+        """the whole list of one bus: channels and their gains, int16 in Q12 (AUDIO_UNITY_GAIN = 1.0), -32767..32767; empty
+        lists clear the bus"""
+        ch = np.ascontiguousarray(channels, dtype=np.uint32).ravel()
+        g = np.ascontiguousarray(gains).ravel()
+        if g.size and (g.min() < -32768 or g.max() > 32767):
+            raise ValueError("a bus gain must fit int16")
+        g = g.astype(np.int16)
+        if g.size != ch.size:
+            raise ValueError(f"{ch.size} channels but {g.size} gains")
+        self._call("set_bus", int(bus), ch.ctypes.data_as(C.POINTER(C.c_uint32)), g.ctypes.data_as(C.POINTER(C.c_int16)), ch.size)
+
+    def set_want(self, want: int, channel: int = ALL):
+        """the tone that opens a channel's squelch: an index into the Tones list, AUDIO_ANY_TONE, or AUDIO_NO_TONE (always
+        open, the default)"""
+        self._call("set_want", int(channel), int(want))
+
+    def reset(self, channel: int = ALL):
+        """zero the filter history and the gate of one channel, or of all"""
+        self._call("reset", int(channel))
+
+    def gate(self, best, present, frame_len: int, group: int) -> np.ndarray:
+        """best, present uint8 [n_channels, F, 4] as Tones.process returns them -> open uint8 [n_channels, n_blocks];
+        blocking"""
+        b = np.ascontiguousarray(best, dtype=np.uint8).reshape(self.n, -1, TONE_GROUPS)
+        p = np.ascontiguousarray(present, dtype=np.uint8).reshape(self.n, -1, TONE_GROUPS)
+        if b.shape != p.shape:
+            raise ValueError(f"best {b.shape} and present {p.shape} differ")
+        n_blocks, rest = divmod(b.shape[1] * int(frame_len), 512)
+        if rest:
+            raise ValueError(f"{b.shape[1]} frames of {frame_len} samples are no whole number of blocks")
+        out = np.zeros((self.n, n_blocks), dtype=np.uint8)
+        self._call("gate", _ptr(b), _ptr(p), int(frame_len), int(group), n_blocks, _ptr(out))
+        return out
+
+    def gate_device(self, d_best, d_present, frame_len: int, group: int, n_blocks: int, d_open, stream=None):
+        """device pointers (ints); asynchronous on stream (None = the handle's own)"""
+        self._call("gate_device", _ptr(d_best), _ptr(d_present), int(frame_len), int(group), int(n_blocks), _ptr(d_open),
+                   _ptr(stream))
+
+    def process(self, pcm: np.ndarray, n_pcm=None, open=None, want_out: bool = True, want_mix: bool = True):
+        """pcm int16 [n_channels, n_blocks, 512], n_pcm uint32 and open uint8 [n_channels, n_blocks] or None -> (out int16
+        [n_channels, n_blocks, 512] or None, mix int16 [n_buses, n_blocks, 512] or None, clips uint32 [n_buses] or None);
+        blocking"""
+        x = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.n, -1)
+        n_blocks = x.shape[1] // 512
+        if x.shape[1] != 512 * n_blocks:
+            raise ValueError(f"a channel's PCM must be whole blocks of 512 samples, got {x.shape[1]} samples")
+        npc = None if n_pcm is None else np.ascontiguousarray(n_pcm, dtype=np.uint32).reshape(self.n, n_blocks)
+        op = None if open is None else np.ascontiguousarray(open, dtype=np.uint8).reshape(self.n, n_blocks)
+        out = np.zeros((self.n, n_blocks, 512), dtype=np.int16) if want_out else None
+        mix = np.zeros((self.m, n_blocks, 512), dtype=np.int16) if want_mix else None
+        clips = np.zeros(self.m, dtype=np.uint32) if want_mix else None
+        self._call("process", _ptr(x), _ptr(npc), _ptr(op), n_blocks, _ptr(out), _ptr(mix), _ptr(clips))
+        return out, mix, clips
+
+    def process_device(self, d_pcm, channel_stride: int, d_n_pcm, d_open, n_blocks: int, d_out=None, out_stride: int = 0,
+                       d_mix=None, d_clips=None, stream=None):
+        """device pointers (ints); d_n_pcm, d_open and any output may be None (not both d_out and d_mix); out_stride 0 =
+        dense rows; asynchronous on stream (None = the handle's own)"""
+        self._call("process_device", _ptr(d_pcm), int(channel_stride), _ptr(d_n_pcm), _ptr(d_open), int(n_blocks), _ptr(d_out),
+                   int(out_stride) if out_stride else 1024 * int(n_blocks), _ptr(d_mix), _ptr(d_clips), _ptr(stream))
+
+
 class Engine:
     """Factory with the interface tests/goldencheck.py expects."""
 

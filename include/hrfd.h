@@ -650,6 +650,83 @@ int hrfd_tone_process_device(hrfd_tone *t, const int16_t *d_pcm, uint64_t channe
                              uint8_t *d_present, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * Audio bank: the PCM of C channels -> every channel's audio behind a voice filter and a click-free gate, and M monitor
+ * mixes of it: what turns the tone bank's verdicts into something a person or a recorder takes (the reference plays its one
+ * channel to a listener; the many-channel counterpart is a mix of the channels that matter).  It reads what
+ * hrfd_rx_process_device / hrfd_ddc_receive write and the tone bank reads: PCM rows [C][n_blocks][512] int16 at 8 kS/s and,
+ * optionally, n_pcm [C][n_blocks].  Exact integer arithmetic, the same on every device (tests/audio_model.py restates it);
+ * shifts are arithmetic:
+ *   sizes     C = 1..65536 channels and M = 1..HRFD_AUDIO_MAX_BUSES = 64 buses, fixed at create; T = 1..HRFD_AUDIO_MAX_TAPS =
+ *             512 taps, one list for every channel; n_blocks = 1..1024.
+ *   input     x[n] = the int16 sample, or 0 where n_pcm is given and the sample's position in its block is
+ *             >= min(n_pcm[c][b], 512): the tone bank's law.  The bytes there do not matter, and that includes their way
+ *             through the filter's history into the next block and the next call.
+ *   filter    h: T int16 taps in Q14 with sum |h| <= 65535 (the bank core's tap check).  acc = sum_k h[k] x[n-k]: |acc| <=
+ *             65535 * 32768 < 2^31 - 2^14, exact in int32 at every partial sum.  y[n] = sat16((acc + 2^13) >> 14).  Default
+ *             h = {16384}: y = x exactly.  The handle keeps the last T - 1 values of x per channel across calls, zeros after
+ *             create and after hrfd_audio_reset, so the outputs of a batch do not depend on how it is cut into calls.
+ *             hrfd_audio_set_taps zeroes every channel's history and gate (it acts as a reset of all channels): samples
+ *             kept for one filter say nothing under another.
+ *   gate      open [C][n_blocks] uint8, 0 = shut, anything else = open; NULL = all open.  p = the gate of the block before,
+ *             q = this block's; for a call's first block p is the handle's per-channel prev: 0 after create and reset, else
+ *             the q of the previous call's last block.  The envelope of sample n = 0..511 of the block: 32768 q where
+ *             p == q; min(32768, 512 (n + 1)) where the gate opens; max(0, 32768 - 512 (n + 1)) where it shuts: a ramp of
+ *             64 samples (8 ms), no clicks.  z[n] = (y[n] e[n] + 2^14) >> 15: y exactly at e = 32768, 0 at e = 0.
+ *   squelch   hrfd_audio_gate* fills `open` from the tone bank's best / present [C][F][4] (F = 512 n_blocks / frame_len;
+ *             frame_len a power of two in 128..8192 with 512 n_blocks a multiple of it, group 0..3): stateless but for
+ *             want[c], a tone index 0..127, HRFD_AUDIO_ANY_TONE or HRFD_AUDIO_NO_TONE (always open; the default).  Frame f
+ *             matches when present[c][f][group] != 0 && (want == ANY || best[c][f][group] == want).  Block b is open when
+ *             want == NO_TONE, or when any frame that overlaps it matches: frames b 512 / L .. (b + 1) 512 / L - 1 for
+ *             L <= 512, the frame b 512 / L (rounded down) for L > 512.  Hang time and debouncing are the caller's policy
+ *             on this per-block gate; a caller with a gate of their own passes their own array to the process call.
+ *   buses     bus m holds a list of N_m <= HRFD_AUDIO_MAX_LIST = 4096 entries, each a channel and a gain: int16 in Q12,
+ *             -32767..32767 (-32768 is refused).  A channel may be on many buses and several times on one.
+ *             s[n] = sum_j g_j z_{c_j}[n], exact in int64 (|s| < 2^42); mix[m][n] = sat16((s + 2^11) >> 12); clips[m] = the
+ *             samples of this call whose saturation changed the value (written, not accumulated).  An empty bus gives
+ *             zeros and 0 clips.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well).  Setters never wait for the
+ * device: what a setter changed is copied to the device on the next call's stream, ahead of its launch.  Calls may use
+ * different streams: each launch is ordered on the device behind the handle's previous one (the history and prev are the
+ * handle's), so a call chains behind the receive and tone calls that filled its input when all are given the same stream.
+ *   hrfd_audio_set_taps        T taps; zeroes every channel's history and prev
+ *   hrfd_audio_set_bus         replaces bus's whole list; n = 0 clears it
+ *   hrfd_audio_set_want        channel: 0..C-1 or HRFD_ALL_CHANNELS
+ *   hrfd_audio_reset           history and prev of one channel, or of all (HRFD_ALL_CHANNELS), from the next call on
+ *   hrfd_audio_gate            host buffers: best, present [C][F][4] -> open [C][n_blocks]; blocking
+ *   hrfd_audio_gate_device     device buffers; asynchronous on `stream` (a hipStream_t, NULL = the handle's own)
+ *   hrfd_audio_process         host buffers, dense: pcm [C][n_blocks][512], n_pcm and open [C][n_blocks] or NULL -> out
+ *                              [C][n_blocks][512] (z), mix [M][n_blocks][512], clips [M]; any output may be NULL, but not
+ *                              both out and mix; blocking
+ *   hrfd_audio_process_device  device buffers; input rows channel_stride_bytes apart, rows of d_out out_stride_bytes apart
+ *                              (both even and >= 1024 n_blocks), d_pcm, d_out and d_mix at any even address, d_clips 4-byte
+ *                              aligned; d_mix dense.  Without d_out, z lives in a buffer of the handle's.  A d_out that
+ *                              overlaps the input is refused: a block needs the raw tail of the block before it.
+ *                              Asynchronous on `stream`
+ */
+typedef struct hrfd_audio hrfd_audio;
+#define HRFD_AUDIO_MAX_BUSES 64
+#define HRFD_AUDIO_MAX_TAPS 512
+#define HRFD_AUDIO_MAX_LIST 4096
+#define HRFD_AUDIO_MAX_BLOCKS 1024
+#define HRFD_AUDIO_ANY_TONE 254
+#define HRFD_AUDIO_NO_TONE 255
+int hrfd_audio_create(uint32_t n_channels, uint32_t n_buses, int device, hrfd_audio **out);
+int hrfd_audio_destroy(hrfd_audio *a);
+int hrfd_audio_set_taps(hrfd_audio *a, const int16_t *taps, uint32_t n);
+int hrfd_audio_set_bus(hrfd_audio *a, uint32_t bus, const uint32_t *channels, const int16_t *gains, uint32_t n);
+int hrfd_audio_set_want(hrfd_audio *a, uint32_t channel, uint32_t want);
+int hrfd_audio_reset(hrfd_audio *a, uint32_t channel);
+int hrfd_audio_gate(hrfd_audio *a, const uint8_t *best, const uint8_t *present, uint32_t frame_len, uint32_t group,
+                    uint32_t n_blocks, uint8_t *open);
+int hrfd_audio_gate_device(hrfd_audio *a, const uint8_t *d_best, const uint8_t *d_present, uint32_t frame_len, uint32_t group,
+                           uint32_t n_blocks, uint8_t *d_open, void *stream);
+int hrfd_audio_process(hrfd_audio *a, const int16_t *pcm, const uint32_t *n_pcm, const uint8_t *open, uint32_t n_blocks,
+                       int16_t *out, int16_t *mix, uint32_t *clips);
+int hrfd_audio_process_device(hrfd_audio *a, const int16_t *d_pcm, uint64_t channel_stride_bytes, const uint32_t *d_n_pcm,
+                              const uint8_t *d_open, uint32_t n_blocks, int16_t *d_out, uint64_t out_stride_bytes, int16_t *d_mix,
+                              uint32_t *d_clips, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",
