@@ -1128,6 +1128,90 @@ class Audio(_Bank):
                    int(out_stride) if out_stride else 1024 * int(n_blocks), _ptr(d_mix), _ptr(d_clips), _ptr(stream))
 
 
+RESAMP_MAX_RATIO = 512
+RESAMP_MAX_TAPS = 16384
+RESAMP_MAX_BRANCH = 512
+RESAMP_MAX_IN = 524288
+
+
+def resample_taps(up: int, down: int, taps_per_branch: int, atten_db: float = None) -> np.ndarray:
+    """int16 taps in Q14 for Resampler(…, up, down).set_taps: a Kaiser-windowed sinc at the prototype rate (up times the
+    input rate), cut off at half the lower of the two rates, DC gain `up`, round(h * 16384), of odd length T = up *
+    taps_per_branch (less one where that is even).  With 8 kS/s as the lower rate the transition band runs from 3.4 to
+    4.6 kHz: atten_db, the Kaiser window's stop-band attenuation, defaults to what the length gives over that band,
+    between 60 and 80 dB (more says nothing behind the rounding to Q14).  A design aid on the host, not part of the bank's
+    exact contract."""
+    L, M, K = int(up), int(down), int(taps_per_branch)
+    if not (1 <= L <= RESAMP_MAX_RATIO and 1 <= M <= RESAMP_MAX_RATIO and 1 <= K <= RESAMP_MAX_BRANCH):
+        raise ValueError(f"up, down and taps_per_branch must be 1..512, got {L}, {M}, {K}")
+    T = L * K - (1 - (L * K) % 2)
+    if T < 3 or T > RESAMP_MAX_TAPS:
+        raise ValueError(f"{L} x {K} taps give a length of {T}: need 3..{RESAMP_MAX_TAPS}")
+    low = max(L, M)                                        # the prototype rate in units of the lower rate
+    width = 2.0 * np.pi * (4600.0 - 3400.0) / TONE_FS / low        # the transition band in radians per prototype sample
+    if atten_db is None:
+        atten_db = min(80.0, max(60.0, 8.0 + 2.285 * width * (T - 1)))
+    a = float(atten_db)
+    beta = 0.1102 * (a - 8.7) if a > 50.0 else (0.5842 * (a - 21.0) ** 0.4 + 0.07886 * (a - 21.0) if a > 21.0 else 0.0)
+    n = np.arange(T, dtype=np.float64) - (T - 1) / 2
+    h = np.sinc(n / low) * np.kaiser(T, beta)
+    h *= L / h.sum()
+    return np.floor(h * 16384.0 + 0.5).astype(np.int16)
+
+
+class Resampler(_Bank):
+    """The resampler bank (hrfd_resamp_*): the PCM of n_channels channels at up / down times its rate, the same rational
+    polyphase filter for every channel: 8 kS/s to a sound card's 48 kS/s with (6, 1), a microphone's 48 kS/s to the
+    modulators' 8 kS/s with (1, 6), 44.1 kS/s with (441, 80) and (80, 441).  Exact in integers and independent of how a stream
+    is cut into calls; a handle other than (1, 1) needs set_taps before its first call (resample_taps designs them)."""
+
+    _prefix = "resamp"
+
+    def __init__(self, n_channels: int, up: int, down: int, device: int = -1):
+        self.n, self.up, self.down = int(n_channels), int(up), int(down)
+        self._create(self.n, self.up, self.down, device)
+
+    def set_taps(self, taps):
+        """1..16384 int16 taps in Q14 at up times the input rate, at most 512 per branch and sum |h| <= 65535 over every
+        branch; zeroes every channel's history and the handle's phase"""
+        t = np.ascontiguousarray(taps, dtype=np.int16).ravel()
+        self._call("set_taps", t.ctypes.data_as(C.POINTER(C.c_int16)), t.size)
+
+    def reset(self, channel: int = ALL):
+        """zero the history of one channel, or the histories of all and the handle's phase"""
+        self._call("reset", int(channel))
+
+    def out_count(self, n_in: int) -> int:
+        """the outputs per channel the next call gives if it takes n_in samples"""
+        v = C.c_uint32(0)
+        self._call("out_count", int(n_in), C.byref(v))
+        return int(v.value)
+
+    def process(self, pcm: np.ndarray, n_pcm=None) -> np.ndarray:
+        """pcm int16 [n_channels, n_in], n_pcm uint32 [n_channels, n_in / 512] or None -> out int16 [n_channels, n_out];
+        blocking"""
+        x = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.n, -1)
+        n_in = x.shape[1]
+        npc = None if n_pcm is None else np.ascontiguousarray(n_pcm, dtype=np.uint32).reshape(self.n, -1)
+        if npc is not None and npc.shape[1] * 512 != n_in:
+            raise ValueError(f"n_pcm needs whole blocks of 512 samples and one entry per block, got {n_in} samples, {npc.shape[1]} entries")
+        cap = max(1, self.out_count(n_in))                 # (a call may give no output; an empty array has no address to pass)
+        out = np.zeros((self.n, cap), dtype=np.int16)
+        v = C.c_uint32(0)
+        self._call("process", _ptr(x), _ptr(npc), n_in, _ptr(out), cap, C.byref(v))
+        return np.ascontiguousarray(out[:, :v.value])
+
+    def process_device(self, d_pcm, channel_stride: int, d_n_pcm, n_in: int, d_out, out_stride: int, out_capacity: int,
+                       stream=None) -> int:
+        """device pointers (ints); d_n_pcm may be None; rows of d_out take out_capacity samples and lie out_stride bytes
+        apart (0 = dense at out_capacity); asynchronous on stream (None = the handle's own).  Returns n_out, the samples
+        written per row"""
+        v = C.c_uint32(0)
+        self._call("process_device", _ptr(d_pcm), int(channel_stride), _ptr(d_n_pcm), int(n_in), _ptr(d_out),
+                   int(out_stride) if out_stride else 2 * int(out_capacity), int(out_capacity), C.byref(v), _ptr(stream))
+        return int(v.value)
+
+
 class Engine:
     """Factory with the interface tests/goldencheck.py expects."""
 

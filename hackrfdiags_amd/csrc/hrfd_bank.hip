@@ -1,4 +1,4 @@
-// hackrfdiags_amd/csrc/hrfd_bank.hip -- the host core of the bank handles (hrfd_ddc, hrfd_duc, hrfd_spec, hrfd_cal, hrfd_tone, hrfd_audio): device and
+// hackrfdiags_amd/csrc/hrfd_bank.hip -- the host core of the bank handles (hrfd_ddc, hrfd_duc, hrfd_spec, hrfd_cal, hrfd_tone, hrfd_audio, hrfd_resamp): device and
 // stream ownership, the three ordering rules, and the argument checks the DDC and the DUC share.  DESIGN.md 3.5a states
 // the rules; hrfd_bank.h holds the parts that need no HIP, hrfd_buf.h the buffers a handle owns (DevBuf, PinnedBuf: shared
 // with the receive and transmit handles).

@@ -727,6 +727,72 @@ int hrfd_audio_process_device(hrfd_audio *a, const int16_t *d_pcm, uint64_t chan
                               uint32_t *d_clips, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * Resampler bank: the PCM of C channels at one rate -> the same audio at L / M times that rate: what stands between the
+ * library's 8 kS/s (the PCM hrfd_rx_process_device / hrfd_ddc_receive write, the audio bank's out and mix rows, the PCM
+ * hrfd_mod / hrfd_duc_transmit read) and the 48, 44.1 or 16 kS/s of sound cards, recorders and codecs.  A rational polyphase
+ * FIR, the same for every channel of a handle.  Exact integer arithmetic, the same on every device and however a stream is
+ * cut into calls (tests/resamp_model.py restates it); shifts are arithmetic, div and mod are those of non-negative integers:
+ *   sizes     C = 1..65536 channels, L = up and M = down in 1..HRFD_RESAMP_MAX_RATIO = 512 with gcd(L, M) = 1 and M <= 8 L,
+ *             all fixed at create.  T = 1..HRFD_RESAMP_MAX_TAPS = 16384 taps with K = ceil(T / L) <=
+ *             HRFD_RESAMP_MAX_BRANCH = 512 taps per branch.  Per call n_in = 1..HRFD_RESAMP_MAX_IN = 524288 samples per
+ *             channel with n_in L < 2^31.  Everything else is refused with HRFD_EINVAL and a text that names the rule.
+ *   taps      h: T int16 in Q14 at the rate L times the input's, h[k] = 0 for k >= T; one list for every channel.  Branch p
+ *             = 0..L-1 holds h[p], h[p + L], ..: sum_k |h[p + k L]| <= 65535 for every branch (the bank core's tap check).
+ *             With it |acc| <= 65535 * 32768 < 2^31 - 2^13: int32 is exact at every partial sum and under the rounding
+ *             constant.  A handle with L = M = 1 starts with {16384}, the identity; any other handle refuses the process
+ *             calls with HRFD_ESTATE until hrfd_resamp_set_taps has been called.  hrfd_resamp_set_taps acts as
+ *             hrfd_resamp_reset(HRFD_ALL_CHANNELS): samples kept for one filter say nothing under another.
+ *   time      the handle (not the channel) keeps one integer d, 0 <= d < M: 0 after create, after hrfd_resamp_set_taps and
+ *             after hrfd_resamp_reset(HRFD_ALL_CHANNELS).  A call of n_in samples gives n_out = 0 if n_in L <= d, else
+ *             ceil((n_in L - d) / M) outputs per channel, the same count for every channel.  Output j = 0..n_out-1 has
+ *             q = d + j M, i = q div L, p = q mod L and
+ *                 y[j] = sat16((sum_{k=0}^{K-1} h[p + k L] x[i - k] + 2^13) >> 14)
+ *             where x[0..n_in-1] is the call's input and x[-1], x[-2], .. are the channel's history: the last K - 1 inputs
+ *             of the calls before, zeros after create and reset.  Afterwards d += n_out M - n_in L, again in 0..M-1.  d
+ *             lives on the host (every n_in is known there), so no call waits for the device.  A call may give no output
+ *             (L = 1, M = 6, n_in = 1 with d > 0): it is valid, moves the history and returns n_out = 0.
+ *             hrfd_resamp_reset(channel) zeroes that channel's history only; d goes on.
+ *   input     rows of n_in int16, channel_stride_bytes apart (even, >= 2 n_in), at even addresses.  n_pcm [C][n_in / 512]
+ *             is optional and accepted only when n_in is a multiple of 512: then x = 0 where a sample's position in its
+ *             block of 512 is >= min(n_pcm[c][b], 512), the tone and audio banks' law; the bytes there do not matter, and
+ *             that includes their way through the history into the next call.  So the bank takes the receive chain's PCM
+ *             and n_pcm directly, the audio bank's out, or its mix rows (C = the number of buses).
+ *   output    rows of n_out int16, out_stride_bytes apart (even, >= 2 out_capacity), at any even address.  out_capacity is
+ *             what a row can take, in samples: a call whose n_out is larger is refused with HRFD_EINVAL before anything is
+ *             launched or any state moves.  *n_out is what the call produced; hrfd_resamp_out_count says beforehand what
+ *             the next call of n_in samples would produce.  Samples n_out..out_capacity-1 of a row are left as they were.
+ *             An out that overlaps the input is refused: other workgroups of the launch still read it.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well).  Setters never wait for the
+ * device: what a setter changed is copied to the device on the next call's stream, ahead of its launch.  Calls may use
+ * different streams: each launch is ordered on the device behind the handle's previous one (the history is the handle's), so
+ * a call chains behind the audio call that filled its input when both are given the same stream.
+ *   hrfd_resamp_create          up = L, down = M
+ *   hrfd_resamp_set_taps        T taps; zeroes every channel's history and d
+ *   hrfd_resamp_reset           the history of one channel, or the histories of all and d (HRFD_ALL_CHANNELS), from the next
+ *                               call on
+ *   hrfd_resamp_out_count       the n_out of the next call, if it takes n_in samples
+ *   hrfd_resamp_process         host buffers, dense: pcm [C][n_in], n_pcm [C][n_in / 512] or NULL -> out, rows of
+ *                               out_capacity samples of which the first *n_out are written; blocking
+ *   hrfd_resamp_process_device  device buffers; asynchronous on `stream` (a hipStream_t, NULL = the handle's own); *n_out is
+ *                               host memory and valid on return
+ */
+typedef struct hrfd_resamp hrfd_resamp;
+#define HRFD_RESAMP_MAX_RATIO 512
+#define HRFD_RESAMP_MAX_TAPS 16384
+#define HRFD_RESAMP_MAX_BRANCH 512
+#define HRFD_RESAMP_MAX_IN 524288
+int hrfd_resamp_create(uint32_t n_channels, uint32_t up, uint32_t down, int device, hrfd_resamp **out);
+int hrfd_resamp_destroy(hrfd_resamp *r);
+int hrfd_resamp_set_taps(hrfd_resamp *r, const int16_t *taps, uint32_t n);
+int hrfd_resamp_reset(hrfd_resamp *r, uint32_t channel);
+int hrfd_resamp_out_count(hrfd_resamp *r, uint32_t n_in, uint32_t *n_out);
+int hrfd_resamp_process(hrfd_resamp *r, const int16_t *pcm, const uint32_t *n_pcm, uint32_t n_in, int16_t *out,
+                        uint32_t out_capacity, uint32_t *n_out);
+int hrfd_resamp_process_device(hrfd_resamp *r, const int16_t *d_pcm, uint64_t channel_stride_bytes, const uint32_t *d_n_pcm,
+                               uint32_t n_in, int16_t *d_out, uint64_t out_stride_bytes, uint32_t out_capacity, uint32_t *n_out,
+                               void *stream);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",
