@@ -6,15 +6,13 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define HRFD_AUDIO_HD __host__ __device__ __forceinline__
-#else
-#define HRFD_AUDIO_HD inline
-#endif
+#include "hrfd_pcm.h"
+
+#define HRFD_AUDIO_HD HRFD_PCM_HD
 
 namespace hrfd {
 
-constexpr uint32_t kAudioBlock = 512;      // PCM samples per block row
+constexpr uint32_t kAudioBlock = kPcmBlock;
 constexpr uint32_t kAudioMaxTaps = 512;
 constexpr uint32_t kAudioMaxBuses = 64;
 constexpr uint32_t kAudioMaxList = 4096;   // entries of one bus
@@ -25,22 +23,7 @@ constexpr uint32_t kAudioNoTone = 255;
 constexpr int32_t kAudioUnity = 32768;     // the envelope of an open gate
 constexpr int32_t kAudioRampStep = 512;    // 64 samples from 0 to kAudioUnity
 
-// ---- 1. input: samples a block gives, min(n_pcm, 512); every block whole when there is no n_pcm
-HRFD_AUDIO_HD uint32_t audio_block_limit(const uint32_t *n_pcm_row, uint32_t block)
-{
-  if (n_pcm_row == nullptr)
-  {
-    return kAudioBlock;
-  }
-  const uint32_t v = n_pcm_row[block];
-  return v < kAudioBlock ? v : kAudioBlock;
-}
-
-HRFD_AUDIO_HD int32_t audio_sat16(int64_t v) { return (int32_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
-
-// ---- 2. voice filter: sum |h| <= 65535 and |x| <= 32768 give |acc| <= 65535 * 32768 = 2^31 - 2^15 < 2^31 - 2^14, so
-// acc + 2^13 stays inside int32 as every partial sum does
-HRFD_AUDIO_HD int32_t audio_fir_round(int32_t acc) { return audio_sat16((int64_t)((acc + (1 << 13)) >> 14)); }
+// ---- 1. input (pcm_block_limit) and 2. voice filter (pcm_fir_round): hrfd_pcm.h
 
 // ---- 3. gate: the envelope of sample n (0..511) of a block whose gate is q behind a block whose gate was p
 HRFD_AUDIO_HD int32_t audio_envelope(bool p, bool q, uint32_t n)
@@ -92,7 +75,7 @@ HRFD_AUDIO_HD bool audio_block_open(const uint8_t *best, const uint8_t *present,
 HRFD_AUDIO_HD int32_t audio_mix_round(int64_t s, bool *clipped)
 {
   const int64_t r = (s + (1 << 11)) >> 12;
-  const int32_t m = audio_sat16(r);
+  const int32_t m = pcm_sat16(r);
   *clipped = (int64_t)m != r;
   return m;
 }
@@ -113,7 +96,7 @@ inline void audio_channel_slow(const int16_t *pcm_row, const uint32_t *n_pcm_row
   for (uint32_t b = 0; b < n_blocks; b++)
   {
     const bool q = open_row == nullptr || open_row[b] != 0, p = *prev != 0;
-    const uint32_t lim = audio_block_limit(n_pcm_row, b);
+    const uint32_t lim = pcm_block_limit(n_pcm_row, b);
     int16_t x[kAudioBlock];
     for (uint32_t n = 0; n < kAudioBlock; n++)
     {
@@ -127,7 +110,7 @@ inline void audio_channel_slow(const int16_t *pcm_row, const uint32_t *n_pcm_row
         const int32_t xv = k <= n ? x[n - k] : hist[H + n - k];
         acc += (int32_t)h[k] * xv;
       }
-      z[b * kAudioBlock + n] = (int16_t)audio_gate(audio_fir_round(acc), audio_envelope(p, q, n));
+      z[b * kAudioBlock + n] = (int16_t)audio_gate(pcm_fir_round(acc), audio_envelope(p, q, n));
     }
     // H < 512: the new history is the block's own tail
     for (uint32_t i = 0; i < H; i++)
@@ -141,10 +124,7 @@ inline void audio_channel_slow(const int16_t *pcm_row, const uint32_t *n_pcm_row
 // ---- the checks, each under `who`, the public function's name
 inline int audio_check_create(const char *who, uint32_t n_channels, uint32_t n_buses, const void *out)
 {
-  if (out == nullptr || n_channels == 0 || n_channels > 65536)
-  {
-    return fail(HRFD_EINVAL, "%s: need 1..65536 channels and a result pointer (got %u)", who, n_channels);
-  }
+  BANK_TRY(pcm_check_channels(who, n_channels, out));
   if (n_buses == 0 || n_buses > kAudioMaxBuses)
   {
     return fail(HRFD_EINVAL, "%s: need 1..%u buses (got %u)", who, kAudioMaxBuses, n_buses);
@@ -152,23 +132,14 @@ inline int audio_check_create(const char *who, uint32_t n_channels, uint32_t n_b
   return HRFD_OK;
 }
 
-// T = 1..512 and the bank core's tap check: sum |h| <= 65535
+// T = 1..512 and the bank core's tap check over the one branch: sum |h| <= 65535
 inline int audio_check_taps(const char *who, const int16_t *taps, uint32_t n)
 {
   if (n == 0 || n > kAudioMaxTaps || taps == nullptr)
   {
     return fail(HRFD_EINVAL, "%s: need 1..%u taps and their array (got %u)", who, kAudioMaxTaps, n);
   }
-  int64_t sum = 0;
-  for (uint32_t k = 0; k < n; k++)
-  {
-    sum += taps[k] < 0 ? -(int64_t)taps[k] : (int64_t)taps[k];
-  }
-  if (sum > 65535)
-  {
-    return fail(HRFD_EINVAL, "%s: sum |h| = %lld > 65535 (the int32 accumulator could overflow)", who, (long long)sum);
-  }
-  return HRFD_OK;
+  return bank_tap_sums_ok(who, taps, n, 1);
 }
 
 // n_channels, n_buses: the handle's, or the largest any handle has where there is none yet
@@ -203,20 +174,7 @@ inline int audio_check_want(const char *who, uint32_t channel, uint32_t want, ui
   {
     return fail(HRFD_EINVAL, "%s: want %u (a tone index 0..127, HRFD_AUDIO_ANY_TONE or HRFD_AUDIO_NO_TONE)", who, want);
   }
-  if (channel >= n_channels && channel != HRFD_ALL_CHANNELS)
-  {
-    return fail(HRFD_EINVAL, "%s: channel %u (0..%u or HRFD_ALL_CHANNELS)", who, channel, n_channels - 1);
-  }
-  return HRFD_OK;
-}
-
-inline int audio_check_reset(const char *who, uint32_t channel, uint32_t n_channels)
-{
-  if (channel >= n_channels && channel != HRFD_ALL_CHANNELS)
-  {
-    return fail(HRFD_EINVAL, "%s: channel %u (0..%u or HRFD_ALL_CHANNELS)", who, channel, n_channels - 1);
-  }
-  return HRFD_OK;
+  return pcm_check_channel(who, channel, n_channels);
 }
 
 inline int audio_check_gate(const char *who, const void *best, const void *present, uint32_t frame_len, uint32_t group,
@@ -226,14 +184,8 @@ inline int audio_check_gate(const char *who, const void *best, const void *prese
   {
     return fail(HRFD_EINVAL, "%s: n_blocks must be 1..%u (got %u)", who, kAudioMaxBlocks, n_blocks);
   }
-  if (frame_len < 128 || frame_len > 8192 || (frame_len & (frame_len - 1)) != 0)
-  {
-    return fail(HRFD_EINVAL, "%s: frame_len must be a power of two, 128..8192 (got %u)", who, frame_len);
-  }
-  if ((kAudioBlock * n_blocks) % frame_len != 0)
-  {
-    return fail(HRFD_EINVAL, "%s: %u blocks of 512 samples are no whole number of frames of %u", who, n_blocks, frame_len);
-  }
+  BANK_TRY(pcm_check_frame_len(who, frame_len));
+  BANK_TRY(pcm_check_frames(who, n_blocks, frame_len));
   if (group >= kAudioGroups)
   {
     return fail(HRFD_EINVAL, "%s: group %u (0..%u)", who, group, kAudioGroups - 1);
@@ -259,21 +211,19 @@ inline int audio_check_call(const char *who, const void *pcm, uint64_t in_stride
     return fail(HRFD_EINVAL, "%s: no output asked for (out and mix are both NULL)", who);
   }
   const uint64_t row = 2ull * kAudioBlock * n_blocks;
-  if (device_entry && ((in_stride & 1u) != 0 || in_stride < row))
+  if (device_entry)
   {
-    return fail(HRFD_EINVAL, "%s: channel_stride_bytes %llu must be even and >= %llu", who, (unsigned long long)in_stride,
-                (unsigned long long)row);
+    BANK_TRY(pcm_check_stride(who, "channel_stride_bytes", in_stride, row));
+    if (out != nullptr)
+    {
+      BANK_TRY(pcm_check_stride(who, "out_stride_bytes", out_stride, row));
+    }
   }
-  if (device_entry && out != nullptr && ((out_stride & 1u) != 0 || out_stride < row))
-  {
-    return fail(HRFD_EINVAL, "%s: out_stride_bytes %llu must be even and >= %llu", who, (unsigned long long)out_stride,
-                (unsigned long long)row);
-  }
-  if (((uintptr_t)pcm & 1u) != 0 || ((uintptr_t)out & 1u) != 0 || ((uintptr_t)mix & 1u) != 0)
+  if (!pcm_aligned(pcm, 2) || !pcm_aligned(out, 2) || !pcm_aligned(mix, 2))
   {
     return fail(HRFD_EINVAL, "%s: the PCM, out and mix must sit at even addresses", who);
   }
-  if (((uintptr_t)clips & 3u) != 0)
+  if (!pcm_aligned(clips, 4))
   {
     return fail(HRFD_EINVAL, "%s: clips must be 4-byte aligned", who);
   }
@@ -283,13 +233,8 @@ inline int audio_check_call(const char *who, const void *pcm, uint64_t in_stride
   }
   if (out != nullptr)
   {
-    const uint64_t is = device_entry ? in_stride : row, os = device_entry ? out_stride : row;
-    const uint64_t a0 = (uint64_t)(uintptr_t)pcm, a1 = a0 + (n_channels - 1) * is + row;
-    const uint64_t b0 = (uint64_t)(uintptr_t)out, b1 = b0 + (n_channels - 1) * os + row;
-    if (a0 < b1 && b0 < a1)
-    {
-      return fail(HRFD_EINVAL, "%s: out overlaps the input (a block needs the raw tail of the block before it)", who);
-    }
+    return pcm_check_no_overlap(who, pcm, device_entry ? in_stride : row, row, out, device_entry ? out_stride : row, row, n_channels,
+                                "a block needs the raw tail of the block before it");
   }
   return HRFD_OK;
 }

@@ -42,7 +42,6 @@ constexpr int kAudioStep = 8;                              // tap dwords of one 
 constexpr int kAudioHistDw = kAudioBlock / 2;              // 256 dwords of history
 constexpr int kAudioXsDw = 4 + (kAudioRun + 1) * kAudioHistDw + 12;      // offset, history, run, what the last step reads over
 constexpr int kAudioMaxJ = (kAudioMaxTaps / 2 + 1 + kAudioStep - 1) / kAudioStep * kAudioStep;      // 264
-constexpr uint32_t kAudioMaxWgs = 1u << 22;                // workgroups of one launch: 2^30 work-items
 static_assert(kAudioRun * kAudioBlock == kAudioThreads * kAudioPer, "one pass of the workgroup covers the run");
 
 typedef uint32_t audio_u4 __attribute__((ext_vector_type(4)));      // 16 bytes of LDS in one read
@@ -113,7 +112,7 @@ __global__ __launch_bounds__(kAudioThreads) void k_audio_fir(const AudioFirParam
     }
     else if (blk <= nb)
     {
-      const uint32_t sb = b0 + blk - 1, lim = audio_block_limit(n_row, sb), pos = 2 * j;
+      const uint32_t sb = b0 + blk - 1, lim = pcm_block_limit(n_row, sb), pos = 2 * j;
       if (pos < lim)
       {
         const int16_t *src = (const int16_t *)((const char *)P.pcm + (uint64_t)c * P.stride) + (uint64_t)sb * kAudioBlock + pos;
@@ -173,8 +172,8 @@ __global__ __launch_bounds__(kAudioThreads) void k_audio_fir(const AudioFirParam
 #pragma unroll
   for (int i = 0; i < kAudioPer; i += 2)
   {
-    const int32_t z0 = audio_gate(audio_fir_round(acc[i]), audio_envelope(p, q, n0 + i));
-    const int32_t z1 = audio_gate(audio_fir_round(acc[i + 1]), audio_envelope(p, q, n0 + i + 1));
+    const int32_t z0 = audio_gate(pcm_fir_round(acc[i]), audio_envelope(p, q, n0 + i));
+    const int32_t z1 = audio_gate(pcm_fir_round(acc[i + 1]), audio_envelope(p, q, n0 + i + 1));
     zd[i / 2] = ((uint32_t)z0 & 0xffffu) | ((uint32_t)z1 << 16);
   }
   int16_t *dst = (int16_t *)((char *)P.out + (uint64_t)c * P.out_stride) + (uint64_t)b0 * kAudioBlock + o;
@@ -298,6 +297,8 @@ __global__ __launch_bounds__(kAudioThreads) void k_audio_gate(const uint8_t *bes
 } // namespace hrfd
 
 // ------------------------------------------------------------------ host side
+static_assert(hrfd::kAudioHistDw == hrfd::BankHistory::kDw, "k_audio_fir reads and writes the core's history rows");
+
 struct hrfd_audio
 {
   hrfd::BankCore core;
@@ -307,17 +308,16 @@ struct hrfd_audio
   std::vector<int16_t> taps;
   std::vector<std::vector<uint32_t>> bus;  // packed entries
   std::vector<uint8_t> bus_dirty;
-  std::vector<uint8_t> want, fresh;        // per channel
-  bool taps_dirty = true, want_dirty = true, any_bus_dirty = true, any_fresh = false;
-  uint32_t side = 0;                       // the ping-pong side the next call reads
+  std::vector<uint8_t> want;               // per channel
+  bool taps_dirty = true, want_dirty = true, any_bus_dirty = true;
+  hrfd::BankHistory hist;                  // the filter's; d_prev follows its sides
 
   // pinned staging: taps, list lengths, want, fresh flags, lists
   hrfd::PinnedBuf<uint8_t> h_stage;
   size_t off_n = 0, off_want = 0, off_fresh = 0, off_list = 0;
   hrfd::DevBuf<uint2> d_taps;              // [kAudioMaxJ]
-  hrfd::DevBuf<uint32_t> d_hist;           // [2][C][256]
-  hrfd::DevBuf<uint8_t> d_prev;            // [2][C]
-  hrfd::DevBuf<uint8_t> d_fresh, d_want;   // [C]
+  hrfd::DevBuf<uint8_t> d_prev;            // [2][C]: the gate of the block before
+  hrfd::DevBuf<uint8_t> d_want;            // [C]
   hrfd::DevBuf<uint32_t> d_list;           // [M][kAudioMaxList]
   hrfd::DevBuf<uint32_t> d_n_list;         // [M]
   hrfd::DevBuf<int16_t> d_z;               // z of a call without d_out
@@ -345,15 +345,13 @@ extern "C" int hrfd_audio_create(uint32_t n_channels, uint32_t n_buses, int devi
   a->bus.resize(M);
   a->bus_dirty.assign(M, 1);
   a->want.assign(C, (uint8_t)kAudioNoTone);
-  a->fresh.assign(C, 0);
   a->off_n = sizeof(uint2) * kAudioMaxJ;
   a->off_want = a->off_n + 4 * M;
   a->off_fresh = a->off_want + C;
   a->off_list = (a->off_fresh + C + 15) / 16 * 16;
-  if (!(a->d_taps.alloc(kAudioMaxJ) && a->d_hist.alloc(2 * C * kAudioHistDw) && a->d_prev.alloc(2 * C) && a->d_fresh.alloc(C) &&
-        a->d_want.alloc(C) && a->d_list.alloc(M * kAudioMaxList) && a->d_n_list.alloc(M) &&
-        a->h_stage.alloc(a->off_list + 4 * M * kAudioMaxList) &&
-        hipMemset(a->d_hist, 0, 4 * 2 * C * kAudioHistDw) == hipSuccess && hipMemset(a->d_prev, 0, 2 * C) == hipSuccess))
+  if (!(a->d_taps.alloc(kAudioMaxJ) && a->hist.alloc(C) && a->d_prev.alloc(2 * C) && a->d_want.alloc(C) &&
+        a->d_list.alloc(M * kAudioMaxList) && a->d_n_list.alloc(M) && a->h_stage.alloc(a->off_list + 4 * M * kAudioMaxList) &&
+        hipMemset(a->d_prev, 0, 2 * C) == hipSuccess))
   {
     (void)hipGetLastError();
     bank_free(a);
@@ -372,29 +370,14 @@ extern "C" int hrfd_audio_destroy(hrfd_audio *a)
   return HRFD_OK;
 }
 
-static void audio_mark_fresh(hrfd_audio *a, uint32_t channel)
-{
-  for (uint32_t c = 0; c < a->n_channels; c++)
-  {
-    if (channel == HRFD_ALL_CHANNELS || c == channel)
-    {
-      a->fresh[c] = 1;
-    }
-  }
-  a->any_fresh = true;
-}
-
 extern "C" int hrfd_audio_set_taps(hrfd_audio *a, const int16_t *taps, uint32_t n)
 {
   BANK_TRY(hrfd::audio_check_taps("hrfd_audio_set_taps", taps, n));
-  if (a == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_audio_set_taps: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_audio_set_taps", a));
   std::lock_guard<std::mutex> g(a->core.mu);
   a->taps.assign(taps, taps + n);
   a->taps_dirty = true;
-  audio_mark_fresh(a, HRFD_ALL_CHANNELS);
+  a->hist.mark(HRFD_ALL_CHANNELS);
   return HRFD_OK;
 }
 
@@ -402,10 +385,7 @@ extern "C" int hrfd_audio_set_bus(hrfd_audio *a, uint32_t bus, const uint32_t *c
 {
   using namespace hrfd;
   BANK_TRY(audio_check_bus("hrfd_audio_set_bus", bus, channels, gains, n, 65536, kAudioMaxBuses));
-  if (a == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_audio_set_bus: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_audio_set_bus", a));
   BANK_TRY(audio_check_bus("hrfd_audio_set_bus", bus, channels, gains, n, a->n_channels, a->n_buses));
   std::lock_guard<std::mutex> g(a->core.mu);
   a->bus[bus].resize(n);
@@ -421,33 +401,21 @@ extern "C" int hrfd_audio_set_bus(hrfd_audio *a, uint32_t bus, const uint32_t *c
 extern "C" int hrfd_audio_set_want(hrfd_audio *a, uint32_t channel, uint32_t want)
 {
   BANK_TRY(hrfd::audio_check_want("hrfd_audio_set_want", channel, want, 65536));
-  if (a == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_audio_set_want: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_audio_set_want", a));
   BANK_TRY(hrfd::audio_check_want("hrfd_audio_set_want", channel, want, a->n_channels));
   std::lock_guard<std::mutex> g(a->core.mu);
-  for (uint32_t c = 0; c < a->n_channels; c++)
-  {
-    if (channel == HRFD_ALL_CHANNELS || c == channel)
-    {
-      a->want[c] = (uint8_t)want;
-    }
-  }
+  hrfd::bank_each_selected(a->n_channels, channel, [&](uint32_t c) { a->want[c] = (uint8_t)want; });
   a->want_dirty = true;
   return HRFD_OK;
 }
 
 extern "C" int hrfd_audio_reset(hrfd_audio *a, uint32_t channel)
 {
-  BANK_TRY(hrfd::audio_check_reset("hrfd_audio_reset", channel, 65536));
-  if (a == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_audio_reset: NULL handle");
-  }
-  BANK_TRY(hrfd::audio_check_reset("hrfd_audio_reset", channel, a->n_channels));
+  BANK_TRY(hrfd::pcm_check_channel("hrfd_audio_reset", channel, 65536));
+  BANK_TRY(hrfd::bank_need_handle("hrfd_audio_reset", a));
+  BANK_TRY(hrfd::pcm_check_channel("hrfd_audio_reset", channel, a->n_channels));
   std::lock_guard<std::mutex> g(a->core.mu);
-  audio_mark_fresh(a, channel);
+  a->hist.mark(channel);
   return HRFD_OK;
 }
 
@@ -480,11 +448,7 @@ static int audio_gate_launch(hrfd_audio *a, const uint8_t *d_best, const uint8_t
   const uint32_t n = a->n_channels * n_blocks;             // <= 2^26
   hipLaunchKernelGGL(k_audio_gate, dim3((n + kAudioThreads - 1) / kAudioThreads), dim3(kAudioThreads), 0, st, d_best, d_present,
                      a->d_want.p, L, group, n_blocks, a->n_channels, d_open);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-  {
-    return fail(HRFD_ENODEV, "k_audio_gate launch failed: %s", hipGetErrorString(e));
-  }
+  BANK_TRY(bank_launch_ok("k_audio_gate"));
   a->core.launched_on(st);
   return HRFD_OK;
 }
@@ -493,10 +457,7 @@ extern "C" int hrfd_audio_gate_device(hrfd_audio *a, const uint8_t *d_best, cons
                                       uint32_t group, uint32_t n_blocks, uint8_t *d_open, void *stream)
 {
   BANK_TRY(hrfd::audio_check_gate("hrfd_audio_gate_device", d_best, d_present, frame_len, group, n_blocks, d_open));
-  if (a == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_audio_gate_device: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_audio_gate_device", a));
   HIP_TRY(hipSetDevice(a->core.device));
   return audio_gate_launch(a, d_best, d_present, frame_len, group, n_blocks, d_open, a->core.stream_or_own(stream));
 }
@@ -506,23 +467,15 @@ extern "C" int hrfd_audio_gate(hrfd_audio *a, const uint8_t *best, const uint8_t
 {
   using namespace hrfd;
   BANK_TRY(audio_check_gate("hrfd_audio_gate", best, present, frame_len, group, n_blocks, open));
-  if (a == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_audio_gate: NULL handle");
-  }
-  HIP_TRY(hipSetDevice(a->core.device));
-  hipStream_t st = a->core.stream;
-  BANK_TRY(a->core.drain());
+  BANK_TRY(hrfd::bank_need_handle("hrfd_audio_gate", a));
+  BankHostCall call(a->core);
   const size_t C = a->n_channels, V = C * (kAudioBlock * n_blocks / frame_len) * kAudioGroups;
-  BANK_TRY(a->d_best.grow_bytes(V));
-  BANK_TRY(a->d_present.grow_bytes(V));
-  BANK_TRY(a->d_open.grow_bytes(C * n_blocks));
-  HIP_TRY(hipMemcpyAsync(a->d_best, best, V, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(a->d_present, present, V, hipMemcpyHostToDevice, st));
-  BANK_TRY(audio_gate_launch(a, a->d_best, a->d_present, frame_len, group, n_blocks, a->d_open, st));
-  HIP_TRY(hipMemcpyAsync(open, a->d_open, C * n_blocks, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return HRFD_OK;
+  const uint8_t *d_best = call.up(a->d_best, best, V), *d_present = call.up(a->d_present, present, V);
+  uint8_t *d_open = call.room(a->d_open, open, C * n_blocks);
+  BANK_TRY(call.rc);
+  BANK_TRY(audio_gate_launch(a, d_best, d_present, frame_len, group, n_blocks, d_open, call.st));
+  call.down(open, d_open, C * n_blocks);
+  return call.finish();
 }
 
 static int audio_check_process(hrfd_audio *a, const char *who, const void *pcm, uint64_t stride, bool device_entry, uint32_t n_blocks,
@@ -530,10 +483,7 @@ static int audio_check_process(hrfd_audio *a, const char *who, const void *pcm, 
 {
   // what the sizes and addresses decide on their own comes first, so that it is refused with its own text
   BANK_TRY(hrfd::audio_check_call(who, pcm, stride, device_entry, n_blocks, out, out_stride, mix, clips, 1));
-  if (a == nullptr)
-  {
-    return fail(HRFD_EINVAL, "%s: NULL handle", who);
-  }
+  BANK_TRY(hrfd::bank_need_handle(who, a));
   return hrfd::audio_check_call(who, pcm, stride, device_entry, n_blocks, out, out_stride, mix, clips, a->n_channels);
 }
 
@@ -555,13 +505,13 @@ static int audio_launch(hrfd_audio *a, const int16_t *d_pcm, uint64_t stride, co
     std::lock_guard<std::mutex> g(a->core.mu);
     P.T = (uint32_t)a->taps.size();
     P.J = ((uint32_t)bank_packed_len((int)P.T) + kAudioStep - 1) / kAudioStep * kAudioStep;
-    P.reset = a->any_fresh ? a->d_fresh.p : nullptr;
-    P.hist_in = a->d_hist + a->side * C * kAudioHistDw;
-    P.hist_out = a->d_hist + (a->side ^ 1u) * C * kAudioHistDw;
-    P.prev_in = a->d_prev + a->side * C;
-    P.prev_out = a->d_prev + (a->side ^ 1u) * C;
-    a->side ^= 1u;
-    if (a->taps_dirty || a->want_dirty || a->any_bus_dirty || a->any_fresh)
+    P.reset = a->hist.reset();
+    P.hist_in = a->hist.in();
+    P.hist_out = a->hist.out();
+    P.prev_in = a->d_prev + a->hist.side * C;
+    P.prev_out = a->d_prev + (a->hist.side ^ 1u) * C;
+    a->hist.flip();
+    if (a->taps_dirty || a->want_dirty || a->any_bus_dirty || a->hist.any_fresh)
     {
       BANK_TRY(a->core.staging_wait());
       if (a->taps_dirty)
@@ -570,12 +520,7 @@ static int audio_launch(hrfd_audio *a, const int16_t *d_pcm, uint64_t stride, co
         HIP_TRY(hipMemcpyAsync(a->d_taps, a->h_stage, sizeof(uint2) * P.J, hipMemcpyHostToDevice, st));
       }
       BANK_TRY(audio_send_want(a, st));
-      if (a->any_fresh)
-      {
-        memcpy(a->h_stage + a->off_fresh, a->fresh.data(), C);
-        HIP_TRY(hipMemcpyAsync(a->d_fresh, a->h_stage + a->off_fresh, C, hipMemcpyHostToDevice, st));
-        a->fresh.assign(C, 0);
-      }
+      BANK_TRY(a->hist.upload(a->h_stage + a->off_fresh, st));
       if (a->any_bus_dirty)
       {
         uint32_t *n_list = (uint32_t *)(a->h_stage + a->off_n);
@@ -592,7 +537,7 @@ static int audio_launch(hrfd_audio *a, const int16_t *d_pcm, uint64_t stride, co
         }
         HIP_TRY(hipMemcpyAsync(a->d_n_list, n_list, 4 * M, hipMemcpyHostToDevice, st));
       }
-      a->taps_dirty = a->any_bus_dirty = a->any_fresh = false;
+      a->taps_dirty = a->any_bus_dirty = false;
       BANK_TRY(a->core.staging_sent(st));
     }
   }
@@ -605,17 +550,9 @@ static int audio_launch(hrfd_audio *a, const int16_t *d_pcm, uint64_t stride, co
   P.n_blocks = n_blocks;
   P.runs = (n_blocks + kAudioRun - 1) / kAudioRun;
   P.n_wgs = a->n_channels * P.runs;                        // <= 2^24
-  for (uint32_t first = 0; first < P.n_wgs; first += kAudioMaxWgs)
-  {
-    P.first_wg = first;
-    hipLaunchKernelGGL(k_audio_fir, dim3(std::min(kAudioMaxWgs, P.n_wgs - first)), dim3(kAudioThreads), 0, st, P,
-                       (const uint2 *)a->d_taps.p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-      return fail(HRFD_ENODEV, "k_audio_fir launch failed: %s", hipGetErrorString(e));
-    }
-  }
+  BANK_TRY(bank_launch_chunked("k_audio_fir", P.n_wgs, P, [&](dim3 grid) {
+    hipLaunchKernelGGL(k_audio_fir, grid, dim3(kAudioThreads), 0, st, P, (const uint2 *)a->d_taps.p);
+  }));
   if (d_mix != nullptr || d_clips != nullptr)
   {
     if (d_clips != nullptr)
@@ -631,11 +568,7 @@ static int audio_launch(hrfd_audio *a, const int16_t *d_pcm, uint64_t stride, co
     Q.clips = d_clips;
     Q.n_blocks = n_blocks;
     hipLaunchKernelGGL(k_audio_mix, dim3(n_blocks, a->n_buses), dim3(kAudioThreads), 0, st, Q);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-      return fail(HRFD_ENODEV, "k_audio_mix launch failed: %s", hipGetErrorString(e));
-    }
+    BANK_TRY(bank_launch_ok("k_audio_mix"));
   }
   a->core.launched_on(st);
   return HRFD_OK;
@@ -657,31 +590,17 @@ extern "C" int hrfd_audio_process(hrfd_audio *a, const int16_t *pcm, const uint3
 {
   using namespace hrfd;
   BANK_TRY(audio_check_process(a, "hrfd_audio_process", pcm, 0, false, n_blocks, out, 0, mix, clips));
-  HIP_TRY(hipSetDevice(a->core.device));
-  hipStream_t st = a->core.stream;
-  BANK_TRY(a->core.drain());
+  BankHostCall call(a->core);
   const size_t C = a->n_channels, M = a->n_buses, row = 2 * (size_t)kAudioBlock * n_blocks;
-  BANK_TRY(a->d_pcm.grow_bytes(row * C));
-  HIP_TRY(hipMemcpyAsync(a->d_pcm, pcm, row * C, hipMemcpyHostToDevice, st));
-  if (n_pcm != nullptr)
-  {
-    BANK_TRY(a->d_n_pcm.grow_bytes(4 * C * n_blocks));
-    HIP_TRY(hipMemcpyAsync(a->d_n_pcm, n_pcm, 4 * C * n_blocks, hipMemcpyHostToDevice, st));
-  }
-  if (open != nullptr)
-  {
-    BANK_TRY(a->d_open.grow_bytes(C * n_blocks));
-    HIP_TRY(hipMemcpyAsync(a->d_open, open, C * n_blocks, hipMemcpyHostToDevice, st));
-  }
-  if (out != nullptr) BANK_TRY(a->d_out.grow_bytes(row * C));
-  if (mix != nullptr) BANK_TRY(a->d_mix.grow_bytes(row * M));
-  if (clips != nullptr) BANK_TRY(a->d_clips.grow_bytes(4 * M));
-  BANK_TRY(audio_launch(a, a->d_pcm, row, n_pcm != nullptr ? a->d_n_pcm.p : nullptr, open != nullptr ? a->d_open.p : nullptr, n_blocks,
-                        out != nullptr ? a->d_out.p : nullptr, row, mix != nullptr ? a->d_mix.p : nullptr,
-                        clips != nullptr ? a->d_clips.p : nullptr, st));
-  if (out != nullptr) HIP_TRY(hipMemcpyAsync(out, a->d_out, row * C, hipMemcpyDeviceToHost, st));
-  if (mix != nullptr) HIP_TRY(hipMemcpyAsync(mix, a->d_mix, row * M, hipMemcpyDeviceToHost, st));
-  if (clips != nullptr) HIP_TRY(hipMemcpyAsync(clips, a->d_clips, 4 * M, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return HRFD_OK;
+  const int16_t *d_pcm = call.up(a->d_pcm, pcm, row * C);
+  const uint32_t *d_n_pcm = call.up(a->d_n_pcm, n_pcm, 4 * C * n_blocks);
+  const uint8_t *d_open = call.up(a->d_open, open, C * n_blocks);
+  int16_t *d_out = call.room(a->d_out, out, row * C), *d_mix = call.room(a->d_mix, mix, row * M);
+  uint32_t *d_clips = call.room(a->d_clips, clips, 4 * M);
+  BANK_TRY(call.rc);
+  BANK_TRY(audio_launch(a, d_pcm, row, d_n_pcm, d_open, n_blocks, d_out, row, d_mix, d_clips, call.st));
+  call.down(out, d_out, row * C);
+  call.down(mix, d_mix, row * M);
+  call.down(clips, d_clips, 4 * M);
+  return call.finish();
 }

@@ -1,6 +1,7 @@
-// hackrfdiags_amd/csrc/hrfd_bank.h -- what the DDC and DUC banks share and no HIP is needed for: the tuning record and
-// its phase law, the tap check and tap packing, and the DUC's per-capture channel lists.  Plain C++ (tests/cpp/san_bank.cc
-// compiles it on the CPU); the includer declares `int fail(int code, const char *fmt, ...)` and the HRFD_* codes first.
+// hackrfdiags_amd/csrc/hrfd_bank.h -- what the banks share and no HIP is needed for: BANK_TRY, the tuning record of the DDC
+// and the DUC and its phase law, the tap check and tap packing of every FIR, and the DUC's per-capture channel lists.
+// hrfd_pcm.h adds the PCM contract on top.  Plain C++ (tests/cpp/san_bank.cc compiles it on the CPU); the includer
+// declares `int fail(int code, const char *fmt, ...)` and the HRFD_* codes first.
 #pragma once
 #include <stdint.h>
 
@@ -11,6 +12,14 @@
 #else
 #define HRFD_BANK_HD inline
 #endif
+
+// return what a check or a step answered unless it is HRFD_OK
+#define BANK_TRY(expr)                                                                   \
+  do                                                                                     \
+  {                                                                                      \
+    const int rc_ = (expr);                                                              \
+    if (rc_ != HRFD_OK) return rc_;                                                      \
+  } while (0)
 
 namespace hrfd {
 

@@ -1,22 +1,20 @@
-// hackrfdiags_amd/csrc/hrfd_bank.hip -- the host core of the bank handles (hrfd_ddc, hrfd_duc, hrfd_spec, hrfd_cal, hrfd_tone, hrfd_audio, hrfd_resamp): device and
-// stream ownership, the three ordering rules, and the argument checks the DDC and the DUC share.  DESIGN.md 3.5a states
-// the rules; hrfd_bank.h holds the parts that need no HIP, hrfd_buf.h the buffers a handle owns (DevBuf, PinnedBuf: shared
-// with the receive and transmit handles).
+// hackrfdiags_amd/csrc/hrfd_bank.hip -- the host core of the bank handles (hrfd_ddc, hrfd_duc, hrfd_spec, hrfd_cal,
+// hrfd_tone, hrfd_audio, hrfd_resamp): device and stream ownership with the three ordering rules (BankCore), what stands
+// around every launch (the NULL-handle refusal, the launch check, the chunked launch, the loop over the selected channels),
+// the blocking host entry (BankHostCall), the history of the PCM banks (BankHistory), and the setters and argument checks
+// the DDC and the DUC share.  DESIGN.md 3.5a states the rules; hrfd_bank.h and hrfd_pcm.h hold the parts that need no HIP,
+// hrfd_buf.h the buffers a handle owns (DevBuf, PinnedBuf: shared with the receive and transmit handles).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
+#include <algorithm>
 #include <mutex>
+#include <vector>
 
 #include "hrfd_bank.h"
 #include "hrfd_buf.h"
 #include "hrfd_ddc_tables.h"
-
-#define BANK_TRY(expr)                                                                   \
-  do                                                                                     \
-  {                                                                                      \
-    const int rc_ = (expr);                                                              \
-    if (rc_ != HRFD_OK) return rc_;                                                      \
-  } while (0)
 
 namespace hrfd {
 
@@ -110,16 +108,166 @@ struct BankCore
   }
 };
 
+// the refusal of a call without a handle, behind what the call's sizes and addresses decide on their own
+static int bank_need_handle(const char *who, const void *handle)
+{
+  return handle != nullptr ? HRFD_OK : fail(HRFD_EINVAL, "%s: NULL handle", who);
+}
+
+// f(i) for item `which` of n, or for every item (HRFD_ALL_CHANNELS); the caller has checked `which`
+template <class F>
+static void bank_each_selected(uint32_t n, uint32_t which, F f)
+{
+  for (uint32_t i = 0; i < n; i++)
+  {
+    if (which == HRFD_ALL_CHANNELS || i == which)
+    {
+      f(i);
+    }
+  }
+}
+
+// behind every kernel launch
+static int bank_launch_ok(const char *kernel)
+{
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? HRFD_OK : fail(HRFD_ENODEV, "%s launch failed: %s", kernel, hipGetErrorString(e));
+}
+
+constexpr uint32_t kBankMaxWgs = 1u << 22; // workgroups of one launch: 2^30 work-items of 256 threads
+
+// n_wgs workgroups in launches of at most kBankMaxWgs: launch(grid) starts one with P.first_wg set to its first workgroup
+template <class Params, class Launch>
+static int bank_launch_chunked(const char *kernel, uint64_t n_wgs, Params &P, Launch launch)
+{
+  for (uint64_t first = 0; first < n_wgs; first += kBankMaxWgs)
+  {
+    P.first_wg = (decltype(P.first_wg))first;
+    launch(dim3((uint32_t)std::min<uint64_t>(kBankMaxWgs, n_wgs - first)));
+    BANK_TRY(bank_launch_ok(kernel));
+  }
+  return HRFD_OK;
+}
+
+// A blocking host entry over a handle's own stream: rc holds the first failure, and every step behind one does nothing.
+//   BankHostCall call(h->core);                           sets the device and drains (rule 3)
+//   d_x = call.up(h->d_x, x, bytes);                      grows the buffer and copies x up; NULL for a NULL x
+//   d_y = call.room(h->d_y, y, bytes);                    grows the buffer of an output; NULL for one not asked for
+//   BANK_TRY(call.rc); BANK_TRY(x_launch(.., call.st));
+//   call.down(y, h->d_y, bytes);                          copies an output back if it was asked for
+//   return call.finish();                                 waits for the stream
+struct BankHostCall
+{
+  hipStream_t st;
+  int rc;
+
+  explicit BankHostCall(BankCore &core) : st(core.stream), rc(begin(core)) {}
+
+  template <class T>
+  T *up(DevBuf<T> &buf, const void *host, size_t bytes)
+  {
+    T *dev = room(buf, host, bytes);
+    if (dev != nullptr)
+    {
+      rc = copy(dev, host, bytes, hipMemcpyHostToDevice);
+    }
+    return rc == HRFD_OK ? dev : nullptr;
+  }
+
+  template <class T>
+  T *room(DevBuf<T> &buf, const void *host, size_t bytes)
+  {
+    if (rc != HRFD_OK || host == nullptr)
+    {
+      return nullptr;
+    }
+    rc = buf.grow_bytes(bytes);
+    return rc == HRFD_OK ? buf.p : nullptr;
+  }
+
+  void down(void *host, const void *dev, size_t bytes)
+  {
+    if (rc == HRFD_OK && host != nullptr)
+    {
+      rc = copy(host, dev, bytes, hipMemcpyDeviceToHost);
+    }
+  }
+
+  int finish()
+  {
+    BANK_TRY(rc);
+    HIP_TRY(hipStreamSynchronize(st));
+    return HRFD_OK;
+  }
+
+private:
+  static int begin(BankCore &core)
+  {
+    HIP_TRY(hipSetDevice(core.device));
+    return core.drain();
+  }
+
+  int copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
+  {
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, st));
+    return HRFD_OK;
+  }
+};
+
+// The filter history of a PCM bank (hrfd_audio, hrfd_resamp): per channel the last 512 samples as the filter saw them, as
+// 256 packed pairs, in a ping-pong of two sides (a launch reads in() and writes out(), flip() turns them over), and the
+// channels that start from zeros with the next launch.  Host fields under the handle's core.mu.
+struct BankHistory
+{
+  static constexpr size_t kDw = 256;       // dwords per channel
+  size_t C = 0;
+  std::vector<uint8_t> fresh;              // per channel
+  bool any_fresh = false;
+  uint32_t side = 0;                       // the side the next launch reads
+  DevBuf<uint32_t> d_hist;                 // [2][C][256]
+  DevBuf<uint8_t> d_fresh;                 // [C]
+
+  bool alloc(size_t n_channels)
+  {
+    C = n_channels;
+    fresh.assign(C, 0);
+    return d_hist.alloc(2 * C * kDw) && d_fresh.alloc(C) && hipMemset(d_hist, 0, 4 * 2 * C * kDw) == hipSuccess;
+  }
+
+  void mark(uint32_t channel)
+  {
+    bank_each_selected((uint32_t)C, channel, [&](uint32_t c) { fresh[c] = 1; });
+    any_fresh = true;
+  }
+
+  // the kernel's reset flags for the next launch, or NULL when no channel is marked; read in front of upload
+  const uint8_t *reset() const { return any_fresh ? d_fresh.p : nullptr; }
+
+  // between staging_wait and staging_sent: the marks go up through `stage`, C bytes of the handle's pinned staging
+  int upload(uint8_t *stage, hipStream_t st)
+  {
+    if (any_fresh)
+    {
+      memcpy(stage, fresh.data(), C);
+      HIP_TRY(hipMemcpyAsync(d_fresh, stage, C, hipMemcpyHostToDevice, st));
+      fresh.assign(C, 0);
+      any_fresh = false;
+    }
+    return HRFD_OK;
+  }
+
+  const uint32_t *in() const { return d_hist + side * C * kDw; }
+  uint32_t *out() const { return d_hist + (side ^ 1u) * C * kDw; }
+  void flip() { side ^= 1u; }
+};
+
 // The setters and getters of a handle with one tuning record per channel (the DDC and the DUC), under `who`, the public
 // function's name.  H has core, n_channels, n_captures, h_chan, N (the absolute wideband sample counter), dirty and
 // clear_history.
 template <class H>
 static int tuned_reset(H *d, const char *who)
 {
-  if (d == nullptr)
-  {
-    return fail(HRFD_EINVAL, "%s: NULL handle", who);
-  }
+  BANK_TRY(bank_need_handle(who, d));
   std::lock_guard<std::mutex> g(d->core.mu);
   d->N = 0;
   for (BankTuning &c : d->h_chan)
@@ -153,13 +301,7 @@ static int tuned_set_word(H *d, const char *who, uint32_t channel, uint32_t valu
     return fail(HRFD_EINVAL, "%s: bad handle or channel", who);
   }
   std::lock_guard<std::mutex> g(d->core.mu);
-  for (uint32_t c = 0; c < d->n_channels; c++)
-  {
-    if (channel == HRFD_ALL_CHANNELS || c == channel)
-    {
-      d->h_chan[c].word = value;
-    }
-  }
+  bank_each_selected(d->n_channels, channel, [&](uint32_t c) { d->h_chan[c].word = value; });
   d->dirty = true;
   return HRFD_OK;
 }

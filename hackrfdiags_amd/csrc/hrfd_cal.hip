@@ -559,11 +559,7 @@ static int cal_launch(hrfd_cal *c, const int8_t *d_in, uint64_t in_stride, uint3
   {
     hipLaunchKernelGGL((k_cal<false, true>), grid, block, 0, st, P);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-  {
-    return fail(HRFD_ENODEV, "k_cal launch failed: %s", hipGetErrorString(e));
-  }
+  BANK_TRY(bank_launch_ok("k_cal"));
   c->core.launched_on(st);
   return HRFD_OK;
 }
@@ -579,28 +575,15 @@ extern "C" int hrfd_cal_process_device(hrfd_cal *c, const int8_t *d_in, uint64_t
 extern "C" int hrfd_cal_process(hrfd_cal *c, const int8_t *captures, uint32_t n_bytes, int8_t *out, int64_t *moments)
 {
   BANK_TRY(cal_check_call(c, captures, n_bytes, n_bytes, out, n_bytes, moments, "hrfd_cal_process"));
-  HIP_TRY(hipSetDevice(c->core.device));
-  hipStream_t st = c->core.stream;
-  BANK_TRY(c->core.drain());
+  hrfd::BankHostCall call(c->core);
   const size_t total = (size_t)n_bytes * c->n_captures, m_total = sizeof(int64_t) * 8 * (size_t)c->n_captures;
-  BANK_TRY(c->d_io.grow_bytes(total));
-  if (moments != nullptr)
-  {
-    BANK_TRY(c->d_moments.grow_bytes(m_total));
-  }
-  HIP_TRY(hipMemcpyAsync(c->d_io, captures, total, hipMemcpyHostToDevice, st));
-  BANK_TRY(cal_launch(c, c->d_io, n_bytes, n_bytes, out != nullptr ? c->d_io.p : nullptr, n_bytes,
-                      moments != nullptr ? c->d_moments.p : nullptr, st));
-  if (out != nullptr)
-  {
-    HIP_TRY(hipMemcpyAsync(out, c->d_io, total, hipMemcpyDeviceToHost, st));
-  }
-  if (moments != nullptr)
-  {
-    HIP_TRY(hipMemcpyAsync(moments, c->d_moments, m_total, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  return HRFD_OK;
+  int8_t *d_io = call.up(c->d_io, captures, total);        // corrected in place when out is asked for
+  unsigned long long *d_moments = call.room(c->d_moments, moments, m_total);
+  BANK_TRY(call.rc);
+  BANK_TRY(cal_launch(c, d_io, n_bytes, n_bytes, out != nullptr ? d_io : nullptr, n_bytes, d_moments, call.st));
+  call.down(out, d_io, total);
+  call.down(moments, d_moments, m_total);
+  return call.finish();
 }
 
 // The operation order is the header's; the library is built without contraction, so no line fuses a multiply and an add.

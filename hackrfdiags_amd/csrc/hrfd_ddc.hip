@@ -483,10 +483,7 @@ extern "C" int hrfd_ddc_set_filter(hrfd_ddc *d, int stage, const int16_t *taps, 
   }
   BANK_TRY(hrfd::bank_tap_count_ok("hrfd_ddc_set_filter", taps, n, stage == 0 ? hrfd::kDdcMaxTA : hrfd::kDdcMaxTB));
   BANK_TRY(hrfd::bank_tap_sums_ok("hrfd_ddc_set_filter", taps, n, 1u));
-  if (d == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_ddc_set_filter: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_ddc_set_filter", d));
   std::lock_guard<std::mutex> g(d->core.mu);
   (stage == 0 ? d->tapsA : d->tapsB).assign(taps, taps + n);
   d->dirty = true;
@@ -555,13 +552,13 @@ static int ddc_launch(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_st
   case 4: hipLaunchKernelGGL(k_ddc<4>, grid, dim3(kDdcThreads), 0, s, P); break;
   default: hipLaunchKernelGGL(k_ddc<8>, grid, dim3(kDdcThreads), 0, s, P); break;
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
+  const int rc = bank_launch_ok("k_ddc");
+  if (rc != HRFD_OK)
   {
     // the counter and the history advance only with a launch that was accepted
     std::lock_guard<std::mutex> g(d->core.mu);
     d->N = P.n0;
-    return fail(HRFD_ENODEV, "k_ddc launch failed: %s", hipGetErrorString(e));
+    return rc;
   }
   d->cur ^= 1;
   d->core.launched_on(s);
@@ -590,17 +587,14 @@ extern "C" int hrfd_ddc_process_device(hrfd_ddc *d, const int8_t *d_captures, ui
 extern "C" int hrfd_ddc_process(hrfd_ddc *d, const int8_t *captures, uint32_t out_bytes, int8_t *out)
 {
   BANK_TRY(ddc_check_call(d, captures, d ? (uint64_t)d->R * out_bytes : 0, out_bytes, out, out_bytes, "hrfd_ddc_process"));
-  HIP_TRY(hipSetDevice(d->core.device));
-  hipStream_t s = d->core.stream;
-  BANK_TRY(d->core.drain());
+  hrfd::BankHostCall call(d->core);
   const size_t in_bytes = (size_t)d->n_captures * d->R * out_bytes, out_total = (size_t)d->n_channels * out_bytes;
-  BANK_TRY(d->d_in.grow_bytes(in_bytes));
-  BANK_TRY(d->d_out.grow_bytes(out_total));
-  HIP_TRY(hipMemcpyAsync(d->d_in, captures, in_bytes, hipMemcpyHostToDevice, s));
-  BANK_TRY(ddc_launch(d, d->d_in, (uint64_t)d->R * out_bytes, out_bytes, d->d_out, out_bytes, s));
-  HIP_TRY(hipMemcpyAsync(out, d->d_out, out_total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return HRFD_OK;
+  const int8_t *d_in = call.up(d->d_in, captures, in_bytes);
+  int8_t *d_out = call.room(d->d_out, out, out_total);
+  BANK_TRY(call.rc);
+  BANK_TRY(ddc_launch(d, d_in, (uint64_t)d->R * out_bytes, out_bytes, d_out, out_bytes, call.st));
+  call.down(out, d_out, out_total);
+  return call.finish();
 }
 
 extern "C" int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captures, uint64_t capture_stride,

@@ -492,10 +492,7 @@ extern "C" int hrfd_duc_set_filter(hrfd_duc *d, int stage, const int16_t *taps, 
   {
     BANK_TRY(hrfd::bank_tap_sums_ok("hrfd_duc_set_filter", taps, n, 1u));
   }
-  if (d == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_duc_set_filter: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_duc_set_filter", d));
   if (stage == 0)
   {
     BANK_TRY(hrfd::bank_tap_sums_ok("hrfd_duc_set_filter", taps, n, d->R));
@@ -603,13 +600,13 @@ static int duc_launch(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_st
   case 4: hipLaunchKernelGGL(k_duc<4>, grid, dim3(kDucThreads), 0, s, P); break;
   default: hipLaunchKernelGGL(k_duc<8>, grid, dim3(kDucThreads), 0, s, P); break;
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
+  const int rc = bank_launch_ok("k_duc");
+  if (rc != HRFD_OK)
   {
     // the counter and the history advance only with a launch that was accepted
     std::lock_guard<std::mutex> g(d->core.mu);
     d->N = P.n0;
-    return fail(HRFD_ENODEV, "k_duc launch failed: %s", hipGetErrorString(e));
+    return rc;
   }
   d->cur ^= 1;
   d->core.launched_on(s);
@@ -638,17 +635,14 @@ extern "C" int hrfd_duc_process_device(hrfd_duc *d, const int8_t *d_channels, ui
 extern "C" int hrfd_duc_process(hrfd_duc *d, const int8_t *channels, uint32_t in_bytes, int8_t *captures)
 {
   BANK_TRY(duc_check_call(d, channels, in_bytes, in_bytes, captures, d ? (uint64_t)d->R * in_bytes : 0, "hrfd_duc_process"));
-  HIP_TRY(hipSetDevice(d->core.device));
-  hipStream_t s = d->core.stream;
-  BANK_TRY(d->core.drain());
+  hrfd::BankHostCall call(d->core);
   const size_t in_total = (size_t)d->n_channels * in_bytes, out_total = (size_t)d->n_captures * d->R * in_bytes;
-  BANK_TRY(d->d_in.grow_bytes(in_total));
-  BANK_TRY(d->d_out.grow_bytes(out_total));
-  HIP_TRY(hipMemcpyAsync(d->d_in, channels, in_total, hipMemcpyHostToDevice, s));
-  BANK_TRY(duc_launch(d, d->d_in, in_bytes, in_bytes, d->d_out, (uint64_t)d->R * in_bytes, s));
-  HIP_TRY(hipMemcpyAsync(captures, d->d_out, out_total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return HRFD_OK;
+  const int8_t *d_in = call.up(d->d_in, channels, in_total);
+  int8_t *d_out = call.room(d->d_out, captures, out_total);
+  BANK_TRY(call.rc);
+  BANK_TRY(duc_launch(d, d_in, in_bytes, in_bytes, d_out, (uint64_t)d->R * in_bytes, call.st));
+  call.down(captures, d_out, out_total);
+  return call.finish();
 }
 
 extern "C" int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pcm, uint32_t n_per_channel,

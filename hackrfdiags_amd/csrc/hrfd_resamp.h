@@ -6,17 +6,13 @@
 #pragma once
 #include <stdint.h>
 
-#include "hrfd_bank.h"
+#include "hrfd_pcm.h"
 
-#if defined(__HIPCC__)
-#define HRFD_RESAMP_HD __host__ __device__ __forceinline__
-#else
-#define HRFD_RESAMP_HD inline
-#endif
+#define HRFD_RESAMP_HD HRFD_PCM_HD
 
 namespace hrfd {
 
-constexpr uint32_t kResampBlock = 512;         // samples per n_pcm block
+constexpr uint32_t kResampBlock = kPcmBlock;   // samples per n_pcm block
 constexpr uint32_t kResampMaxRatio = 512;      // L and M
 constexpr uint32_t kResampMaxDown = 8;         // M <= 8 L
 constexpr uint32_t kResampMaxTaps = 16384;     // T
@@ -24,16 +20,7 @@ constexpr uint32_t kResampMaxBranch = 512;     // K = ceil(T / L)
 constexpr uint32_t kResampMaxIn = 524288;      // n_in of one call
 constexpr uint32_t kResampHist = 512;          // samples of history kept per channel, whatever K is
 
-// ---- 1. input: samples a block gives, min(n_pcm, 512); every block whole when there is no n_pcm
-HRFD_RESAMP_HD uint32_t resamp_block_limit(const uint32_t *n_pcm_row, uint32_t block)
-{
-  if (n_pcm_row == nullptr)
-  {
-    return kResampBlock;
-  }
-  const uint32_t v = n_pcm_row[block];
-  return v < kResampBlock ? v : kResampBlock;
-}
+// ---- 1. input (pcm_block_limit) and 3. rounding (pcm_fir_round, over every branch's sum |h| <= 65535): hrfd_pcm.h
 
 HRFD_RESAMP_HD uint32_t resamp_gcd(uint32_t a, uint32_t b)
 {
@@ -61,14 +48,6 @@ HRFD_RESAMP_HD uint32_t resamp_advance(uint32_t d, uint32_t n_in, uint32_t n_out
   return (uint32_t)((int64_t)d + (int64_t)n_out * M - (int64_t)n_in * L);
 }
 
-// ---- 3. rounding: every branch has sum |h| <= 65535 and |x| <= 32768, so |acc| <= 65535 * 32768 = 2^31 - 2^15 <
-// 2^31 - 2^13: acc + 2^13 stays inside int32 as every partial sum does
-HRFD_RESAMP_HD int32_t resamp_round(int32_t acc)
-{
-  const int32_t v = (acc + (1 << 13)) >> 14;
-  return v < -32768 ? -32768 : (v > 32767 ? 32767 : v);
-}
-
 // ---- one channel, output by output (the contract as a loop; the kernel must agree bit for bit)
 // x_row: the channel's n_in samples; n_pcm_row: its [n_in / 512] or NULL; h: T taps; hist: the last 512 values of x in time
 // order (hist[511] is the newest), read and replaced; y: resamp_out_count(n_in, L, M, d) outputs.  Returns the next d.
@@ -82,7 +61,7 @@ inline uint32_t resamp_channel_slow(const int16_t *x_row, const uint32_t *n_pcm_
       return hist[(int64_t)kResampHist + s];
     }
     const uint32_t b = (uint32_t)s / kResampBlock, pos = (uint32_t)s % kResampBlock;
-    return pos < resamp_block_limit(n_pcm_row, b) ? x_row[s] : 0;
+    return pos < pcm_block_limit(n_pcm_row, b) ? x_row[s] : 0;
   };
   for (uint32_t j = 0; j < n_out; j++)
   {
@@ -95,7 +74,7 @@ inline uint32_t resamp_channel_slow(const int16_t *x_row, const uint32_t *n_pcm_
       const uint32_t t = p + k * L;
       acc += (t < T ? (int32_t)h[t] : 0) * x(i - (int64_t)k);
     }
-    y[j] = (int16_t)resamp_round(acc);
+    y[j] = (int16_t)pcm_fir_round(acc);
   }
   int16_t next[kResampHist];
   for (uint32_t m = 0; m < kResampHist; m++)
@@ -112,10 +91,7 @@ inline uint32_t resamp_channel_slow(const int16_t *x_row, const uint32_t *n_pcm_
 // ---- the checks, each under `who`, the public function's name
 inline int resamp_check_create(const char *who, uint32_t n_channels, uint32_t L, uint32_t M, const void *out)
 {
-  if (out == nullptr || n_channels == 0 || n_channels > 65536)
-  {
-    return fail(HRFD_EINVAL, "%s: need 1..65536 channels and a result pointer (got %u)", who, n_channels);
-  }
+  BANK_TRY(pcm_check_channels(who, n_channels, out));
   if (L == 0 || L > kResampMaxRatio || M == 0 || M > kResampMaxRatio)
   {
     return fail(HRFD_EINVAL, "%s: up and down must be 1..%u (got %u / %u)", who, kResampMaxRatio, L, M);
@@ -144,26 +120,13 @@ inline int resamp_check_tap_list(const char *who, const int16_t *taps, uint32_t 
 // and with the handle's L: K = ceil(T / L) <= 512 and the bank core's tap check over the L branches
 inline int resamp_check_taps(const char *who, const int16_t *taps, uint32_t n, uint32_t L)
 {
-  const int rc = resamp_check_tap_list(who, taps, n);
-  if (rc != HRFD_OK)
-  {
-    return rc;
-  }
+  BANK_TRY(resamp_check_tap_list(who, taps, n));
   if (resamp_branch_taps(n, L) > kResampMaxBranch)
   {
     return fail(HRFD_EINVAL, "%s: %u taps over %u branches are %u taps per branch (at most %u)", who, n, L, resamp_branch_taps(n, L),
                 kResampMaxBranch);
   }
   return bank_tap_sums_ok(who, taps, n, L);
-}
-
-inline int resamp_check_reset(const char *who, uint32_t channel, uint32_t n_channels)
-{
-  if (channel >= n_channels && channel != HRFD_ALL_CHANNELS)
-  {
-    return fail(HRFD_EINVAL, "%s: channel %u (0..%u or HRFD_ALL_CHANNELS)", who, channel, n_channels - 1);
-  }
-  return HRFD_OK;
 }
 
 inline int resamp_check_n_in(const char *who, uint32_t n_in)
@@ -200,31 +163,22 @@ inline int resamp_check_capacity(const char *who, uint32_t n_out, uint32_t out_c
 inline int resamp_check_call(const char *who, const void *pcm, uint64_t in_stride, bool device_entry, const void *n_pcm, uint32_t n_in,
                              const void *out, uint64_t out_stride, uint32_t out_capacity, const void *n_out, uint32_t n_channels)
 {
-  const int rc = resamp_check_n_in(who, n_in);
-  if (rc != HRFD_OK)
-  {
-    return rc;
-  }
+  BANK_TRY(resamp_check_n_in(who, n_in));
   if (n_pcm != nullptr && n_in % kResampBlock != 0)
   {
     return fail(HRFD_EINVAL, "%s: n_pcm needs n_in to be a multiple of %u (got %u)", who, kResampBlock, n_in);
   }
   const uint64_t row = 2ull * n_in, out_row = 2ull * out_capacity;
-  if (device_entry && ((in_stride & 1u) != 0 || in_stride < row))
+  if (device_entry)
   {
-    return fail(HRFD_EINVAL, "%s: channel_stride_bytes %llu must be even and >= %llu", who, (unsigned long long)in_stride,
-                (unsigned long long)row);
+    BANK_TRY(pcm_check_stride(who, "channel_stride_bytes", in_stride, row));
+    BANK_TRY(pcm_check_stride(who, "out_stride_bytes", out_stride, out_row, " (2 x out_capacity)"));
   }
-  if (device_entry && ((out_stride & 1u) != 0 || out_stride < out_row))
-  {
-    return fail(HRFD_EINVAL, "%s: out_stride_bytes %llu must be even and >= %llu (2 x out_capacity)", who,
-                (unsigned long long)out_stride, (unsigned long long)out_row);
-  }
-  if (((uintptr_t)pcm & 1u) != 0 || ((uintptr_t)out & 1u) != 0)
+  if (!pcm_aligned(pcm, 2) || !pcm_aligned(out, 2))
   {
     return fail(HRFD_EINVAL, "%s: the PCM and out must sit at even addresses", who);
   }
-  if (((uintptr_t)n_pcm & 3u) != 0)
+  if (!pcm_aligned(n_pcm, 4))
   {
     return fail(HRFD_EINVAL, "%s: n_pcm must be 4-byte aligned", who);
   }
@@ -232,14 +186,8 @@ inline int resamp_check_call(const char *who, const void *pcm, uint64_t in_strid
   {
     return fail(HRFD_EINVAL, "%s: NULL argument", who);
   }
-  const uint64_t is = device_entry ? in_stride : row, os = device_entry ? out_stride : out_row;
-  const uint64_t a0 = (uint64_t)(uintptr_t)pcm, a1 = a0 + (n_channels - 1) * is + row;
-  const uint64_t b0 = (uint64_t)(uintptr_t)out, b1 = b0 + (n_channels - 1) * os + out_row;
-  if (a0 < b1 && b0 < a1)
-  {
-    return fail(HRFD_EINVAL, "%s: out overlaps the input (other workgroups still read it)", who);
-  }
-  return HRFD_OK;
+  return pcm_check_no_overlap(who, pcm, device_entry ? in_stride : row, row, out, device_entry ? out_stride : out_row, out_row,
+                              n_channels, "other workgroups still read it");
 }
 
 } // namespace hrfd

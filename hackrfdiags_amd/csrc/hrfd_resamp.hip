@@ -40,7 +40,6 @@ constexpr int kResampHistDw = kResampHist / 2;             // 256 dwords of hist
 constexpr int kResampMaxJ4 = (kResampMaxBranch / 2 + 1 + 3) / 4 * 4;      // 260
 // the last window starts at most (kResampTile - 1) * 8 + 1 samples behind the first dword, and reads J4 dwords
 constexpr int kResampXsDw = ((kResampTile - 1) * (int)kResampMaxDown + 1) / 2 + kResampMaxJ4;      // 4352
-constexpr uint32_t kResampMaxWgs = 1u << 22;               // workgroups of one launch: 2^30 work-items
 static_assert(kResampHistDw == kResampThreads, "one dword of the next history per thread");
 static_assert(kResampXsDw * 4 < 18 * 1024, "the tile stays under 18 KB of LDS");
 
@@ -72,7 +71,7 @@ __device__ __forceinline__ uint32_t resamp_pair(const ResampParams &P, const int
   {
     return 0u;
   }
-  const uint32_t pos = (uint32_t)s % kResampBlock, lim = resamp_block_limit(n_row, (uint32_t)s / kResampBlock);
+  const uint32_t pos = (uint32_t)s % kResampBlock, lim = pcm_block_limit(n_row, (uint32_t)s / kResampBlock);
   if (pos >= lim)
   {
     return 0u;
@@ -158,7 +157,7 @@ __global__ __launch_bounds__(kResampThreads) void k_resamp(const ResampParams P,
         acc = dot2(win[jb + 2], tv.z, acc);
         acc = dot2(win[jb + 3], tv.w, acc);
       }
-      y[t] = resamp_round(acc);
+      y[t] = pcm_fir_round(acc);
       i += P.Mq;
       p += P.Mr;
       if (p >= P.L)
@@ -201,6 +200,8 @@ static inline size_t resamp_taps_dw(uint32_t L)
 } // namespace hrfd
 
 // ------------------------------------------------------------------ host side
+static_assert(hrfd::kResampHistDw == hrfd::BankHistory::kDw, "k_resamp reads and writes the core's history rows");
+
 struct hrfd_resamp
 {
   hrfd::BankCore core;
@@ -208,17 +209,14 @@ struct hrfd_resamp
 
   // host settings, under core.mu
   std::vector<int16_t> taps;               // empty = none set yet
-  std::vector<uint8_t> fresh;              // per channel
-  bool taps_dirty = true, any_fresh = false;
+  bool taps_dirty = true;
   uint32_t d = 0;                          // the phase of the next call's first output, 0..M-1
-  uint32_t side = 0;                       // the ping-pong side the next call reads
+  hrfd::BankHistory hist;
 
   // pinned staging: the packed taps, then the fresh flags
   hrfd::PinnedBuf<uint8_t> h_stage;
   size_t off_fresh = 0;
   hrfd::DevBuf<uint32_t> d_taps;           // [L][2][J4]
-  hrfd::DevBuf<uint32_t> d_hist;           // [2][C][256]
-  hrfd::DevBuf<uint8_t> d_fresh;           // [C]
 
   // host-path staging
   hrfd::DevBuf<int16_t> d_pcm, d_out;
@@ -243,10 +241,8 @@ extern "C" int hrfd_resamp_create(uint32_t n_channels, uint32_t up, uint32_t dow
   {
     r->taps.assign(1, (int16_t)16384);
   }
-  r->fresh.assign(C, 0);
   r->off_fresh = 4 * resamp_taps_dw(up);
-  if (!(r->d_taps.alloc(resamp_taps_dw(up)) && r->d_hist.alloc(2 * C * kResampHistDw) && r->d_fresh.alloc(C) &&
-        r->h_stage.alloc(r->off_fresh + C) && hipMemset(r->d_hist, 0, 4 * 2 * C * kResampHistDw) == hipSuccess))
+  if (!(r->d_taps.alloc(resamp_taps_dw(up)) && r->hist.alloc(C) && r->h_stage.alloc(r->off_fresh + C)))
   {
     (void)hipGetLastError();
     bank_free(r);
@@ -265,17 +261,10 @@ extern "C" int hrfd_resamp_destroy(hrfd_resamp *r)
   return HRFD_OK;
 }
 
-// under core.mu
+// under core.mu: a reset of all channels also takes the phase back to 0
 static void resamp_mark_fresh(hrfd_resamp *r, uint32_t channel)
 {
-  for (uint32_t c = 0; c < r->n_channels; c++)
-  {
-    if (channel == HRFD_ALL_CHANNELS || c == channel)
-    {
-      r->fresh[c] = 1;
-    }
-  }
-  r->any_fresh = true;
+  r->hist.mark(channel);
   if (channel == HRFD_ALL_CHANNELS)
   {
     r->d = 0;
@@ -285,10 +274,7 @@ static void resamp_mark_fresh(hrfd_resamp *r, uint32_t channel)
 extern "C" int hrfd_resamp_set_taps(hrfd_resamp *r, const int16_t *taps, uint32_t n)
 {
   BANK_TRY(hrfd::resamp_check_tap_list("hrfd_resamp_set_taps", taps, n));
-  if (r == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_resamp_set_taps: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_resamp_set_taps", r));
   BANK_TRY(hrfd::resamp_check_taps("hrfd_resamp_set_taps", taps, n, r->L));
   std::lock_guard<std::mutex> g(r->core.mu);
   r->taps.assign(taps, taps + n);
@@ -299,12 +285,9 @@ extern "C" int hrfd_resamp_set_taps(hrfd_resamp *r, const int16_t *taps, uint32_
 
 extern "C" int hrfd_resamp_reset(hrfd_resamp *r, uint32_t channel)
 {
-  BANK_TRY(hrfd::resamp_check_reset("hrfd_resamp_reset", channel, 65536));
-  if (r == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_resamp_reset: NULL handle");
-  }
-  BANK_TRY(hrfd::resamp_check_reset("hrfd_resamp_reset", channel, r->n_channels));
+  BANK_TRY(hrfd::pcm_check_channel("hrfd_resamp_reset", channel, 65536));
+  BANK_TRY(hrfd::bank_need_handle("hrfd_resamp_reset", r));
+  BANK_TRY(hrfd::pcm_check_channel("hrfd_resamp_reset", channel, r->n_channels));
   std::lock_guard<std::mutex> g(r->core.mu);
   resamp_mark_fresh(r, channel);
   return HRFD_OK;
@@ -318,10 +301,7 @@ extern "C" int hrfd_resamp_out_count(hrfd_resamp *r, uint32_t n_in, uint32_t *n_
   {
     return fail(HRFD_EINVAL, "hrfd_resamp_out_count: NULL argument");
   }
-  if (r == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_resamp_out_count: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_resamp_out_count", r));
   BANK_TRY(resamp_check_span("hrfd_resamp_out_count", n_in, r->L));
   std::lock_guard<std::mutex> g(r->core.mu);
   *n_out = resamp_out_count(n_in, r->L, r->M, r->d);
@@ -333,10 +313,7 @@ static int resamp_check_process(hrfd_resamp *r, const char *who, const void *pcm
 {
   // what the sizes and addresses decide on their own comes first, so that it is refused with its own text
   BANK_TRY(hrfd::resamp_check_call(who, pcm, stride, device_entry, n_pcm, n_in, out, out_stride, out_capacity, n_out, 1));
-  if (r == nullptr)
-  {
-    return fail(HRFD_EINVAL, "%s: NULL handle", who);
-  }
+  BANK_TRY(hrfd::bank_need_handle(who, r));
   BANK_TRY(hrfd::resamp_check_call(who, pcm, stride, device_entry, n_pcm, n_in, out, out_stride, out_capacity, n_out, r->n_channels));
   BANK_TRY(hrfd::resamp_check_span(who, n_in, r->L));
   // before a buffer grows or a copy starts; resamp_launch looks again under the lock that moves d
@@ -373,7 +350,6 @@ static int resamp_launch(hrfd_resamp *r, const char *who, const int16_t *d_pcm, 
                          int16_t *d_out, uint64_t out_stride, uint32_t out_capacity, bool dense_out, uint32_t *n_out, hipStream_t st)
 {
   using namespace hrfd;
-  const size_t C = r->n_channels;
   ResampParams P;
   {
     std::lock_guard<std::mutex> g(r->core.mu);
@@ -386,10 +362,10 @@ static int resamp_launch(hrfd_resamp *r, const char *who, const int16_t *d_pcm, 
     BANK_TRY(r->core.order_behind_last(st));
     P.K = resamp_branch_taps((uint32_t)r->taps.size(), r->L);
     P.J4 = resamp_j4(P.K);
-    P.reset = r->any_fresh ? r->d_fresh.p : nullptr;
-    P.hist_in = r->d_hist + r->side * C * kResampHistDw;
-    P.hist_out = r->d_hist + (r->side ^ 1u) * C * kResampHistDw;
-    if (r->taps_dirty || r->any_fresh)
+    P.reset = r->hist.reset();
+    P.hist_in = r->hist.in();
+    P.hist_out = r->hist.out();
+    if (r->taps_dirty || r->hist.any_fresh)
     {
       BANK_TRY(r->core.staging_wait());
       if (r->taps_dirty)
@@ -397,18 +373,13 @@ static int resamp_launch(hrfd_resamp *r, const char *who, const int16_t *d_pcm, 
         resamp_stage_taps(r, P.K, P.J4);
         HIP_TRY(hipMemcpyAsync(r->d_taps, r->h_stage, 4 * (size_t)r->L * 2 * P.J4, hipMemcpyHostToDevice, st));
       }
-      if (r->any_fresh)
-      {
-        memcpy(r->h_stage + r->off_fresh, r->fresh.data(), C);
-        HIP_TRY(hipMemcpyAsync(r->d_fresh, r->h_stage + r->off_fresh, C, hipMemcpyHostToDevice, st));
-        r->fresh.assign(C, 0);
-      }
-      r->taps_dirty = r->any_fresh = false;
+      BANK_TRY(r->hist.upload(r->h_stage + r->off_fresh, st));
+      r->taps_dirty = false;
       BANK_TRY(r->core.staging_sent(st));
     }
     P.d = r->d;
     r->d = resamp_advance(r->d, n_in, P.n_out, r->L, r->M);
-    r->side ^= 1u;
+    r->hist.flip();
   }
   P.pcm = d_pcm;
   P.stride = stride;
@@ -421,18 +392,9 @@ static int resamp_launch(hrfd_resamp *r, const char *who, const int16_t *d_pcm, 
   P.M = r->M;
   P.Mq = r->M / r->L;
   P.Mr = r->M % r->L;
-  const uint64_t n_wgs = (uint64_t)r->n_channels * P.tiles;
-  for (uint64_t first = 0; first < n_wgs; first += kResampMaxWgs)
-  {
-    P.first_wg = first;
-    hipLaunchKernelGGL(k_resamp, dim3((uint32_t)std::min<uint64_t>(kResampMaxWgs, n_wgs - first)), dim3(kResampThreads), 0, st, P,
-                       (const uint32_t *)r->d_taps.p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-      return fail(HRFD_ENODEV, "k_resamp launch failed: %s", hipGetErrorString(e));
-    }
-  }
+  BANK_TRY(bank_launch_chunked("k_resamp", (uint64_t)r->n_channels * P.tiles, P, [&](dim3 grid) {
+    hipLaunchKernelGGL(k_resamp, grid, dim3(kResampThreads), 0, st, P, (const uint32_t *)r->d_taps.p);
+  }));
   r->core.launched_on(st);
   *n_out = P.n_out;
   return HRFD_OK;
@@ -455,27 +417,20 @@ extern "C" int hrfd_resamp_process(hrfd_resamp *r, const int16_t *pcm, const uin
   using namespace hrfd;
   const char *who = "hrfd_resamp_process";
   BANK_TRY(resamp_check_process(r, who, pcm, 0, false, n_pcm, n_in, out, 0, out_capacity, n_out));
-  HIP_TRY(hipSetDevice(r->core.device));
-  hipStream_t st = r->core.stream;
-  BANK_TRY(r->core.drain());
+  BankHostCall call(r->core);
   const size_t C = r->n_channels, row = 2 * (size_t)n_in;
-  BANK_TRY(r->d_pcm.grow_bytes(row * C));
-  BANK_TRY(r->d_out.grow_bytes(std::max<size_t>(16, 2 * (size_t)out_capacity * C)));
-  HIP_TRY(hipMemcpyAsync(r->d_pcm, pcm, row * C, hipMemcpyHostToDevice, st));
-  if (n_pcm != nullptr)
-  {
-    const size_t bytes = 4 * C * (n_in / kResampBlock);
-    BANK_TRY(r->d_n_pcm.grow_bytes(bytes));
-    HIP_TRY(hipMemcpyAsync(r->d_n_pcm, n_pcm, bytes, hipMemcpyHostToDevice, st));
-  }
+  const int16_t *d_pcm = call.up(r->d_pcm, pcm, row * C);
+  const uint32_t *d_n_pcm = call.up(r->d_n_pcm, n_pcm, 4 * C * (n_in / kResampBlock));
+  int16_t *d_out = call.room(r->d_out, out, std::max<size_t>(16, 2 * (size_t)out_capacity * C));
+  BANK_TRY(call.rc);
   uint32_t n = 0;
-  // the device rows are dense at n_out, the caller's out_capacity samples apart
-  BANK_TRY(resamp_launch(r, who, r->d_pcm, row, n_pcm != nullptr ? r->d_n_pcm.p : nullptr, n_in, r->d_out, 0, out_capacity, true, &n, st));
+  // the device rows are dense at n_out, the caller's out_capacity samples apart: a strided copy of its own brings them back
+  BANK_TRY(resamp_launch(r, who, d_pcm, row, d_n_pcm, n_in, d_out, 0, out_capacity, true, &n, call.st));
   if (n != 0)
   {
-    HIP_TRY(hipMemcpy2DAsync(out, 2 * (size_t)out_capacity, r->d_out, 2 * (size_t)n, 2 * (size_t)n, C, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpy2DAsync(out, 2 * (size_t)out_capacity, d_out, 2 * (size_t)n, 2 * (size_t)n, C, hipMemcpyDeviceToHost, call.st));
   }
-  HIP_TRY(hipStreamSynchronize(st));
+  BANK_TRY(call.finish());
   *n_out = n;
   return HRFD_OK;
 }

@@ -479,10 +479,7 @@ extern "C" int hrfd_spec_destroy(hrfd_spec *s)
 
 extern "C" int hrfd_spec_set_window(hrfd_spec *s, const int16_t *w)
 {
-  if (s == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_spec_set_window: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_spec_set_window", s));
   std::lock_guard<std::mutex> g(s->core.mu);
   if (w == nullptr)
   {
@@ -528,10 +525,7 @@ extern "C" int hrfd_spec_set_band(hrfd_spec *s, uint32_t band, uint32_t capture,
 
 extern "C" int hrfd_spec_clear_bands(hrfd_spec *s)
 {
-  if (s == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_spec_clear_bands: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_spec_clear_bands", s));
   std::lock_guard<std::mutex> g(s->core.mu);
   s->bands.clear();
   s->dirty_bands = true;
@@ -650,16 +644,12 @@ static int spec_launch(hrfd_spec *s, const int8_t *d_captures, uint64_t capture_
   case 12: hipLaunchKernelGGL(k_spec<12>, grid, dim3(spec_threads(12)), 0, st, P); break;
   default: hipLaunchKernelGGL(k_spec<13>, grid, dim3(spec_threads(13)), 0, st, P); break;
   }
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && K > 0)
+  BANK_TRY(bank_launch_ok("k_spec"));
+  if (K > 0)
   {
     hipLaunchKernelGGL(k_spec_bands, dim3(K), dim3(kSpecBandThreads), 0, st, d_power, s->d_bands, s->N, n_frames, d_band_power,
                        d_present);
-    e = hipGetLastError();
-  }
-  if (e != hipSuccess)
-  {
-    return fail(HRFD_ENODEV, "k_spec launch failed: %s", hipGetErrorString(e));
+    BANK_TRY(bank_launch_ok("k_spec"));
   }
   s->core.launched_on(st);
   return HRFD_OK;
@@ -678,9 +668,7 @@ extern "C" int hrfd_spec_process(hrfd_spec *s, const int8_t *captures, uint32_t 
                                  uint8_t *present)
 {
   BANK_TRY(spec_check_call(s, captures, s ? 2ull * s->N * n_frames : 0, n_frames, power, band_power, present, "hrfd_spec_process"));
-  HIP_TRY(hipSetDevice(s->core.device));
-  hipStream_t st = s->core.stream;
-  BANK_TRY(s->core.drain());
+  hrfd::BankHostCall call(s->core);
   uint32_t K;
   {
     std::lock_guard<std::mutex> g(s->core.mu);
@@ -688,22 +676,21 @@ extern "C" int hrfd_spec_process(hrfd_spec *s, const int8_t *captures, uint32_t 
   }
   const size_t row = 2 * (size_t)s->N * n_frames, in_total = row * s->n_captures;
   const size_t p_total = sizeof(uint64_t) * (size_t)s->n_captures * s->N;
-  BANK_TRY(s->d_in.grow_bytes(in_total));
-  BANK_TRY(s->d_power.grow_bytes(p_total));
-  if (K > 0)
+  if (K == 0 || band_power == nullptr || present == nullptr)
   {
-    BANK_TRY(s->d_band_power.grow_bytes(sizeof(uint64_t) * K));
-    BANK_TRY(s->d_present.grow_bytes(K));
+    K = 0;                                                 // no bands, or bands set behind the check: they wait a call
+    band_power = nullptr;
+    present = nullptr;
   }
-  HIP_TRY(hipMemcpyAsync(s->d_in, captures, in_total, hipMemcpyHostToDevice, st));
-  BANK_TRY(spec_launch(s, s->d_in, row, n_frames, s->d_power, s->d_band_power, s->d_present, K, st));
-  HIP_TRY(hipMemcpyAsync(power, s->d_power, p_total, hipMemcpyDeviceToHost, st));
-  if (K > 0)
-  {
-    HIP_TRY(hipMemcpyAsync(band_power, s->d_band_power, sizeof(uint64_t) * K, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(present, s->d_present, K, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  return HRFD_OK;
+  const int8_t *d_in = call.up(s->d_in, captures, in_total);
+  unsigned long long *d_power = call.room(s->d_power, power, p_total);
+  unsigned long long *d_band_power = call.room(s->d_band_power, band_power, sizeof(uint64_t) * K);
+  uint8_t *d_present = call.room(s->d_present, present, K);
+  BANK_TRY(call.rc);
+  BANK_TRY(spec_launch(s, d_in, row, n_frames, d_power, d_band_power, d_present, K, call.st));
+  call.down(power, d_power, p_total);
+  call.down(band_power, d_band_power, sizeof(uint64_t) * K);
+  call.down(present, d_present, K);
+  return call.finish();
 }
 #endif /* HRFD_SPEC_KERNEL_ONLY */

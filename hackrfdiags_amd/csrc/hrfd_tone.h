@@ -6,15 +6,13 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define HRFD_TONE_HD __host__ __device__ __forceinline__
-#else
-#define HRFD_TONE_HD inline
-#endif
+#include "hrfd_pcm.h"
+
+#define HRFD_TONE_HD HRFD_PCM_HD
 
 namespace hrfd {
 
-constexpr uint32_t kToneBlock = 512;       // PCM samples per block row
+constexpr uint32_t kToneBlock = kPcmBlock;
 constexpr uint32_t kToneGroups = 4;
 constexpr uint32_t kToneMaxTones = 128;
 constexpr uint32_t kToneNoBest = 255;
@@ -35,17 +33,6 @@ HRFD_TONE_HD uint64_t tone_power(int64_t I, int64_t Q)
   return (uint64_t)(i * i) + (uint64_t)(q * q);
 }
 
-// samples a block gives: min(n_pcm, 512), every block whole when there is no n_pcm
-HRFD_TONE_HD uint32_t tone_block_limit(const uint32_t *n_pcm_row, uint32_t block)
-{
-  if (n_pcm_row == nullptr)
-  {
-    return kToneBlock;
-  }
-  const uint32_t v = n_pcm_row[block];
-  return v < kToneBlock ? v : kToneBlock;
-}
-
 // valid[c][f]: the samples of frame f (L samples from sample f L of the channel) below their block's limit.
 // n_pcm_row: the channel's [n_blocks] or NULL
 HRFD_TONE_HD uint32_t tone_frame_valid(const uint32_t *n_pcm_row, uint32_t frame, uint32_t L)
@@ -56,11 +43,11 @@ HRFD_TONE_HD uint32_t tone_frame_valid(const uint32_t *n_pcm_row, uint32_t frame
     const uint32_t per = L / kToneBlock;
     for (uint32_t b = 0; b < per; b++)
     {
-      v += tone_block_limit(n_pcm_row, frame * per + b);
+      v += pcm_block_limit(n_pcm_row, frame * per + b);
     }
     return v;
   }
-  const uint32_t per = kToneBlock / L, pos = (frame % per) * L, lim = tone_block_limit(n_pcm_row, frame / per);
+  const uint32_t per = kToneBlock / L, pos = (frame % per) * L, lim = pcm_block_limit(n_pcm_row, frame / per);
   return lim <= pos ? 0u : (lim - pos < L ? lim - pos : L);
 }
 
@@ -109,7 +96,7 @@ inline void tone_frame_slow(const int16_t *pcm_row, const uint32_t *n_pcm_row, u
     for (uint32_t n = 0; n < L; n++)
     {
       const uint32_t j = frame * L + n, b = j / kToneBlock, pos = j % kToneBlock;
-      const int32_t x = pos < tone_block_limit(n_pcm_row, b) ? pcm_row[j] : 0;
+      const int32_t x = pos < pcm_block_limit(n_pcm_row, b) ? pcm_row[j] : 0;
       const int32_t u = tone_window(x, window[n]);
       const uint32_t i = tone_cos_index(steps[k] * n);
       I += (int64_t)u * cos_table[i];
@@ -149,19 +136,10 @@ inline void tone_frame_slow(const int16_t *pcm_row, const uint32_t *n_pcm_row, u
 }
 
 // ---- the checks, each under `who`, the public function's name
-inline bool tone_frame_len_ok(uint32_t L) { return L >= 128 && L <= 8192 && (L & (L - 1)) == 0; }
-
 inline int tone_check_create(const char *who, uint32_t n_channels, uint32_t frame_len, const void *out)
 {
-  if (out == nullptr || n_channels == 0 || n_channels > 65536)
-  {
-    return fail(HRFD_EINVAL, "%s: need 1..65536 channels and a result pointer (got %u)", who, n_channels);
-  }
-  if (!tone_frame_len_ok(frame_len))
-  {
-    return fail(HRFD_EINVAL, "%s: frame_len must be a power of two, 128..8192 (got %u)", who, frame_len);
-  }
-  return HRFD_OK;
+  BANK_TRY(pcm_check_channels(who, n_channels, out));
+  return pcm_check_frame_len(who, frame_len);
 }
 
 inline int tone_check_tones(const char *who, const uint32_t *steps, const uint8_t *groups, uint32_t K)
@@ -221,16 +199,15 @@ inline int tone_check_call(const char *who, const void *pcm, uint64_t channel_st
   {
     return fail(HRFD_EINVAL, "%s: no output asked for", who);
   }
-  if (device_entry && ((channel_stride & 1u) != 0 || channel_stride < 2ull * kToneBlock * n_blocks))
+  if (device_entry)
   {
-    return fail(HRFD_EINVAL, "%s: channel_stride_bytes %llu must be even and >= %u", who, (unsigned long long)channel_stride,
-                2u * kToneBlock * n_blocks);
+    BANK_TRY(pcm_check_stride(who, "channel_stride_bytes", channel_stride, 2ull * kToneBlock * n_blocks));
   }
-  if (((uintptr_t)pcm & 1u) != 0)
+  if (!pcm_aligned(pcm, 2))
   {
     return fail(HRFD_EINVAL, "%s: the PCM must sit at an even address", who);
   }
-  if (((uintptr_t)power & 7u) != 0 || ((uintptr_t)energy & 7u) != 0 || ((uintptr_t)valid & 3u) != 0)
+  if (!pcm_aligned(power, 8) || !pcm_aligned(energy, 8) || !pcm_aligned(valid, 4))
   {
     return fail(HRFD_EINVAL, "%s: power and energy must be 8-byte aligned, valid 4-byte aligned", who);
   }
@@ -244,10 +221,7 @@ inline int tone_check_call(const char *who, const void *pcm, uint64_t channel_st
 // what the handle's frame length and tone count decide
 inline int tone_check_frames(const char *who, uint32_t L, uint32_t n_blocks, uint32_t n_tones)
 {
-  if ((kToneBlock * n_blocks) % L != 0)
-  {
-    return fail(HRFD_EINVAL, "%s: %u blocks of 512 samples are no whole number of frames of %u", who, n_blocks, L);
-  }
+  BANK_TRY(pcm_check_frames(who, n_blocks, L));
   if (n_tones == 0)
   {
     return fail(HRFD_EINVAL, "%s: no tones set (hrfd_tone_set_tones comes first)", who);

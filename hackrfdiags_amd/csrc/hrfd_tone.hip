@@ -35,7 +35,6 @@ constexpr int kToneThreads = 256;
 constexpr int kToneWaves = kToneThreads / 64;
 constexpr int kToneTile = 16384;           // samples of one workgroup's frames
 constexpr int kToneMaxFrames = 16;         // frames of one workgroup
-constexpr uint32_t kToneMaxWgs = 1u << 22; // workgroups of one launch: 2^30 work-items
 
 typedef short tone_s2 __attribute__((ext_vector_type(2)));
 // signed 16-bit dot product of two dwords plus acc, without clamping; device code only
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(kToneThreads) void k_tone(const ToneParams P)
     {
       const uint32_t c = (uint32_t)g / F, fr = (uint32_t)g - c * F;
       const uint32_t js = fr * L + 2 * j, pos = js & (kToneBlock - 1);
-      const uint32_t lim = tone_block_limit(P.n_pcm != nullptr ? P.n_pcm + (uint64_t)c * P.n_blocks : nullptr, js / kToneBlock);
+      const uint32_t lim = pcm_block_limit(P.n_pcm != nullptr ? P.n_pcm + (uint64_t)c * P.n_blocks : nullptr, js / kToneBlock);
       const int16_t *row = (const int16_t *)((const char *)P.pcm + (uint64_t)c * P.stride) + js;
       int32_t x0 = 0, x1 = 0;
       if (pos < lim)
@@ -344,10 +343,7 @@ extern "C" int hrfd_tone_destroy(hrfd_tone *t)
 extern "C" int hrfd_tone_set_tones(hrfd_tone *t, const uint32_t *steps, const uint8_t *groups, uint32_t n_tones)
 {
   BANK_TRY(hrfd::tone_check_tones("hrfd_tone_set_tones", steps, groups, n_tones));
-  if (t == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_tone_set_tones: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_tone_set_tones", t));
   std::lock_guard<std::mutex> g(t->core.mu);
   t->steps.assign(steps, steps + n_tones);
   if (groups != nullptr)
@@ -375,10 +371,7 @@ extern "C" int hrfd_tone_n_tones(hrfd_tone *t, uint32_t *n_tones)
 
 extern "C" int hrfd_tone_set_window(hrfd_tone *t, const int16_t *w)
 {
-  if (t == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_tone_set_window: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_tone_set_window", t));
   BANK_TRY(hrfd::tone_check_window("hrfd_tone_set_window", w, t->L));
   std::lock_guard<std::mutex> g(t->core.mu);
   if (w == nullptr)
@@ -396,19 +389,12 @@ extern "C" int hrfd_tone_set_window(hrfd_tone *t, const int16_t *w)
 extern "C" int hrfd_tone_set_threshold(hrfd_tone *t, uint32_t group, uint32_t ratio_q8, uint64_t min_energy)
 {
   BANK_TRY(hrfd::tone_check_threshold("hrfd_tone_set_threshold", group, ratio_q8, min_energy));
-  if (t == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_tone_set_threshold: NULL handle");
-  }
+  BANK_TRY(hrfd::bank_need_handle("hrfd_tone_set_threshold", t));
   std::lock_guard<std::mutex> g(t->core.mu);
-  for (uint32_t i = 0; i < hrfd::kToneGroups; i++)
-  {
-    if (group == HRFD_ALL_CHANNELS || i == group)
-    {
-      t->th.ratio_q8[i] = ratio_q8;
-      t->th.min_energy[i] = min_energy;
-    }
-  }
+  hrfd::bank_each_selected(hrfd::kToneGroups, group, [&](uint32_t i) {
+    t->th.ratio_q8[i] = ratio_q8;
+    t->th.min_energy[i] = min_energy;
+  });
   return HRFD_OK;
 }
 
@@ -418,10 +404,7 @@ static int tone_check_process(hrfd_tone *t, const char *who, const void *pcm, ui
 {
   // what the sizes and addresses decide on their own comes first, so that it is refused with its own text
   BANK_TRY(hrfd::tone_check_call(who, pcm, stride, device_entry, n_blocks, power, energy, valid, best, present));
-  if (t == nullptr)
-  {
-    return fail(HRFD_EINVAL, "%s: NULL handle", who);
-  }
+  BANK_TRY(hrfd::bank_need_handle(who, t));
   std::lock_guard<std::mutex> g(t->core.mu);
   return hrfd::tone_check_frames(who, t->L, n_blocks, (uint32_t)t->steps.size());
 }
@@ -456,11 +439,7 @@ static int tone_launch(hrfd_tone *t, const int16_t *d_pcm, uint64_t stride, cons
         const uint32_t entries = P.K * (L / 2);
         hipLaunchKernelGGL(k_tone_table, dim3((entries + kToneThreads - 1) / kToneThreads), dim3(kToneThreads), 0, st, t->d_cs.p,
                            t->d_steps.p, t->d_table.p, L, P.K);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-        {
-          return fail(HRFD_ENODEV, "k_tone_table launch failed: %s", hipGetErrorString(e));
-        }
+        BANK_TRY(bank_launch_ok("k_tone_table"));
       }
       t->window_dirty = t->tones_dirty = false;
       BANK_TRY(t->core.staging_sent(st));
@@ -481,11 +460,8 @@ static int tone_launch(hrfd_tone *t, const int16_t *d_pcm, uint64_t stride, cons
   P.F = kToneBlock * n_blocks / L;
   P.G = t->n_channels * P.F;
   const uint32_t FT = std::min((uint32_t)kToneMaxFrames, (uint32_t)kToneTile / L);
-  const uint32_t wgs = (P.G + FT - 1) / FT;
-  for (uint32_t first = 0; first < wgs; first += kToneMaxWgs)
-  {
-    P.first_wg = first;
-    const dim3 grid(std::min(kToneMaxWgs, wgs - first)), block(kToneThreads);
+  BANK_TRY(bank_launch_chunked("k_tone", (P.G + FT - 1) / FT, P, [&](dim3 grid) {
+    const dim3 block(kToneThreads);
     switch (FT)
     {
     case 16: hipLaunchKernelGGL(k_tone<16>, grid, block, 0, st, P); break;
@@ -493,12 +469,7 @@ static int tone_launch(hrfd_tone *t, const int16_t *d_pcm, uint64_t stride, cons
     case 4: hipLaunchKernelGGL(k_tone<4>, grid, block, 0, st, P); break;
     default: hipLaunchKernelGGL(k_tone<2>, grid, block, 0, st, P); break;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-      return fail(HRFD_ENODEV, "k_tone launch failed: %s", hipGetErrorString(e));
-    }
-  }
+  }));
   t->core.launched_on(st);
   return HRFD_OK;
 }
@@ -519,9 +490,7 @@ extern "C" int hrfd_tone_process(hrfd_tone *t, const int16_t *pcm, const uint32_
 {
   using namespace hrfd;
   BANK_TRY(tone_check_process(t, "hrfd_tone_process", pcm, 0, false, n_blocks, power, energy, valid, best, present));
-  HIP_TRY(hipSetDevice(t->core.device));
-  hipStream_t st = t->core.stream;
-  BANK_TRY(t->core.drain());
+  BankHostCall call(t->core);
   uint32_t K;
   {
     std::lock_guard<std::mutex> g(t->core.mu);
@@ -529,26 +498,17 @@ extern "C" int hrfd_tone_process(hrfd_tone *t, const int16_t *pcm, const uint32_
   }
   const size_t C = t->n_channels, G = C * (kToneBlock * n_blocks / t->L);
   const size_t row = 2 * (size_t)kToneBlock * n_blocks;
-  BANK_TRY(t->d_pcm.grow_bytes(row * C));
-  HIP_TRY(hipMemcpyAsync(t->d_pcm, pcm, row * C, hipMemcpyHostToDevice, st));
-  if (n_pcm != nullptr)
-  {
-    BANK_TRY(t->d_n_pcm.grow_bytes(4 * C * n_blocks));
-    HIP_TRY(hipMemcpyAsync(t->d_n_pcm, n_pcm, 4 * C * n_blocks, hipMemcpyHostToDevice, st));
-  }
-  if (power != nullptr) BANK_TRY(t->d_power.grow_bytes(8 * G * K));
-  if (energy != nullptr) BANK_TRY(t->d_energy.grow_bytes(8 * G));
-  if (valid != nullptr) BANK_TRY(t->d_valid.grow_bytes(4 * G));
-  if (best != nullptr) BANK_TRY(t->d_best.grow_bytes(kToneGroups * G));
-  if (present != nullptr) BANK_TRY(t->d_present.grow_bytes(kToneGroups * G));
-  BANK_TRY(tone_launch(t, t->d_pcm, row, n_pcm != nullptr ? t->d_n_pcm.p : nullptr, n_blocks, power != nullptr ? t->d_power.p : nullptr,
-                       energy != nullptr ? t->d_energy.p : nullptr, valid != nullptr ? t->d_valid.p : nullptr,
-                       best != nullptr ? t->d_best.p : nullptr, present != nullptr ? t->d_present.p : nullptr, st));
-  if (power != nullptr) HIP_TRY(hipMemcpyAsync(power, t->d_power, 8 * G * K, hipMemcpyDeviceToHost, st));
-  if (energy != nullptr) HIP_TRY(hipMemcpyAsync(energy, t->d_energy, 8 * G, hipMemcpyDeviceToHost, st));
-  if (valid != nullptr) HIP_TRY(hipMemcpyAsync(valid, t->d_valid, 4 * G, hipMemcpyDeviceToHost, st));
-  if (best != nullptr) HIP_TRY(hipMemcpyAsync(best, t->d_best, kToneGroups * G, hipMemcpyDeviceToHost, st));
-  if (present != nullptr) HIP_TRY(hipMemcpyAsync(present, t->d_present, kToneGroups * G, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return HRFD_OK;
+  const int16_t *d_pcm = call.up(t->d_pcm, pcm, row * C);
+  const uint32_t *d_n_pcm = call.up(t->d_n_pcm, n_pcm, 4 * C * n_blocks);
+  uint64_t *d_power = call.room(t->d_power, power, 8 * G * K), *d_energy = call.room(t->d_energy, energy, 8 * G);
+  uint32_t *d_valid = call.room(t->d_valid, valid, 4 * G);
+  uint8_t *d_best = call.room(t->d_best, best, kToneGroups * G), *d_present = call.room(t->d_present, present, kToneGroups * G);
+  BANK_TRY(call.rc);
+  BANK_TRY(tone_launch(t, d_pcm, row, d_n_pcm, n_blocks, d_power, d_energy, d_valid, d_best, d_present, call.st));
+  call.down(power, d_power, 8 * G * K);
+  call.down(energy, d_energy, 8 * G);
+  call.down(valid, d_valid, 4 * G);
+  call.down(best, d_best, kToneGroups * G);
+  call.down(present, d_present, kToneGroups * G);
+  return call.finish();
 }

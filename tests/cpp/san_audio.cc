@@ -89,8 +89,8 @@ static int check_the_checks()
   }
   CHECK(refused(audio_check_want("who", 5, 0, 5), "channel 5"));
   CHECK(audio_check_want("who", HRFD_ALL_CHANNELS, 254, 5) == HRFD_OK && audio_check_want("who", 4, 255, 5) == HRFD_OK);
-  CHECK(refused(audio_check_reset("who", 5, 5), "channel 5") && audio_check_reset("who", 4, 5) == HRFD_OK);
-  CHECK(audio_check_reset("who", HRFD_ALL_CHANNELS, 1) == HRFD_OK);
+  CHECK(refused(pcm_check_channel("who", 5, 5), "channel 5") && pcm_check_channel("who", 4, 5) == HRFD_OK);
+  CHECK(pcm_check_channel("who", HRFD_ALL_CHANNELS, 1) == HRFD_OK);
 
   alignas(16) static char buf[16384];
   const void *p = buf;
@@ -140,16 +140,7 @@ static int check_the_checks()
 
 static int check_laws()
 {
-  // rounding and saturation of the filter: (acc + 2^13) >> 14 at 32767, 32768, -32768, -32769
-  CHECK(audio_fir_round(32767 * 16384 + 8191) == 32767 && audio_fir_round(32767 * 16384 + 8192) == 32767);
-  CHECK(audio_fir_round(32766 * 16384 + 8192) == 32767 && audio_fir_round(32766 * 16384 + 8191) == 32766);
-  CHECK(audio_fir_round(-32768 * 16384 - 8192) == -32768 && audio_fir_round(-32768 * 16384 - 8193) == -32768);
-  CHECK(audio_fir_round(-32767 * 16384 - 8193) == -32768 && audio_fir_round(-32767 * 16384 - 8192) == -32767);
-  CHECK(audio_fir_round(-1) == 0 && audio_fir_round(-8192) == 0 && audio_fir_round(-8193) == -1 && audio_fir_round(8191) == 0);
-  // the largest accumulators the tap check allows
-  const int64_t top = 65535ll * 32768;
-  CHECK(top < (1ll << 31) - (1 << 14));
-  CHECK(audio_fir_round((int32_t)top) == 32767 && audio_fir_round((int32_t)-top) == -32768);
+  // the filter's rounding and saturation (pcm_fir_round): tests/cpp/san_pcm.cc
   // the envelope: 64 samples, monotonic, exact ends
   for (uint32_t n = 0; n < 512; n++)
   {
@@ -245,7 +236,7 @@ static int check_cutting_and_n_pcm()
     other = pcm;
     for (uint32_t b = 0; b < n_blocks; b++)
     {
-      for (uint32_t n = audio_block_limit(n_pcm, b); n < 512; n++)
+      for (uint32_t n = pcm_block_limit(n_pcm, b); n < 512; n++)
       {
         other[512 * b + n] ^= 0x5a5a;
       }

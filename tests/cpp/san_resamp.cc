@@ -1,6 +1,6 @@
 // Sanitizer harness for the HIP-free part of the resampler bank (hackrfdiags_amd/csrc/hrfd_resamp.h), CPU only: compiled as
 // plain C++ under -fsanitize=address,undefined (tests/test_resamp_sanitizers.py).  Every check at its limit with its text,
-// the count and phase law over every ratio's edge, the rounding on its boundaries, the slow loop at the largest sums the laws
+// the count and phase law over every ratio's edge (the rounding on its boundaries: san_pcm.cc), the slow loop at the largest sums the laws
 // allow (a branch sum of 65535 against +-32768 samples, K = 512), a stream cut into calls against one long call with calls
 // that give no output, and n_pcm with other bytes behind it.
 #include <stdarg.h>
@@ -78,8 +78,8 @@ static int check_the_checks()
   CHECK(refused(resamp_check_taps("who", b.data(), 9, 3), "branch 1 of 3 has sum |h| = 65536"));
   CHECK(resamp_check_taps("who", b.data(), 7, 3) == HRFD_OK);           // h[k] = 0 for k >= T
 
-  CHECK(refused(resamp_check_reset("who", 5, 5), "channel 5") && resamp_check_reset("who", 4, 5) == HRFD_OK);
-  CHECK(resamp_check_reset("who", HRFD_ALL_CHANNELS, 1) == HRFD_OK);
+  CHECK(refused(pcm_check_channel("who", 5, 5), "channel 5") && pcm_check_channel("who", 4, 5) == HRFD_OK);
+  CHECK(pcm_check_channel("who", HRFD_ALL_CHANNELS, 1) == HRFD_OK);
   CHECK(refused(resamp_check_n_in("who", 0), "n_in") && refused(resamp_check_n_in("who", 524289), "n_in"));
   CHECK(resamp_check_n_in("who", 1) == HRFD_OK && resamp_check_n_in("who", 524288) == HRFD_OK);
   // no call can reach this one (524288 x 512 = 2^28); the kernel's 32-bit q rests on it all the same
@@ -119,15 +119,7 @@ static int check_the_checks()
 
 static int check_laws()
 {
-  // rounding and saturation: (acc + 2^13) >> 14 at 32767, 32768, -32768, -32769
-  CHECK(resamp_round(32767 * 16384 + 8191) == 32767 && resamp_round(32767 * 16384 + 8192) == 32767);
-  CHECK(resamp_round(32766 * 16384 + 8192) == 32767 && resamp_round(32766 * 16384 + 8191) == 32766);
-  CHECK(resamp_round(-32768 * 16384 - 8192) == -32768 && resamp_round(-32768 * 16384 - 8193) == -32768);
-  CHECK(resamp_round(-32767 * 16384 - 8193) == -32768 && resamp_round(-32767 * 16384 - 8192) == -32767);
-  CHECK(resamp_round(-1) == 0 && resamp_round(-8192) == 0 && resamp_round(-8193) == -1 && resamp_round(8191) == 0);
-  const int64_t top = 65535ll * 32768;
-  CHECK(top < (1ll << 31) - (1 << 13));
-  CHECK(resamp_round((int32_t)top) == 32767 && resamp_round((int32_t)-top) == -32768);
+  // rounding and saturation (pcm_fir_round): tests/cpp/san_pcm.cc
   // count and phase: the outputs are those whose q lies below n_in L, and d stays in 0..M-1; a stream of single samples
   // and one of the largest calls give every output once
   for (uint32_t L : {1u, 2u, 3u, 5u, 7u, 80u, 147u, 441u, 511u, 512u})

@@ -123,7 +123,7 @@ static int check_valid()
         for (uint32_t n = 0; n < L; n++)
         {
           const uint32_t j = f * L + n;
-          want += j % 512 < tone_block_limit(n_pcm, j / 512) ? 1 : 0;
+          want += j % 512 < pcm_block_limit(n_pcm, j / 512) ? 1 : 0;
         }
         CHECK(tone_frame_valid(n_pcm, f, L) == want);
         CHECK(tone_frame_valid(nullptr, f, L) == L);

@@ -45,6 +45,24 @@ def test_bank_core_under_sanitizers(tmp_path):
     assert r.returncode == 0 and "san_bank ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
 
 
+def test_pcm_contract_under_sanitizers(tmp_path):
+    """The PCM contract the tone, audio and resampler banks share (hackrfdiags_amd/csrc/hrfd_pcm.h: the block limit, the FIR
+    rounding, the shared argument checks with their texts, the overlap check) compiled into tests/cpp/san_pcm.cc under
+    -fsanitize=address,undefined and run."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "san_pcm")
+    cmd = ["g++", "-x", "c++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+           os.path.join(HERE, "cpp", "san_pcm.cc")]
+    b = subprocess.run(cmd, capture_output=True, text=True, cwd=os.path.join(HERE, "cpp"))
+    if b.returncode != 0 and ("cannot find" in b.stderr or "unrecognized" in b.stderr):
+        pytest.skip("this toolchain has no runtime for -fsanitize=address,undefined")
+    assert b.returncode == 0, b.stderr[-2000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0 and "san_pcm ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
+
+
 def test_rx_plan_under_sanitizers(tmp_path):
     """The HIP-free part of the receive launch (hackrfdiags_amd/csrc/hrfd_rx_plan.h: geometry, channel lists, the plan)
     compiled into tests/cpp/san_rx_plan.cc under -fsanitize=address,undefined and run: the lists against brute force, the
