@@ -223,6 +223,8 @@ def load() -> C.CDLL:
         L.hrfd_tone_set_threshold.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint64]
         L.hrfd_tone_process.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]
         L.hrfd_tone_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]
+        if hasattr(L, "hrfd_tone_debug_set_max_wgs"):     # (an older build named by HRFD_LIB has none)
+            L.hrfd_tone_debug_set_max_wgs.argtypes = [_vp, C.c_uint32]
     if hasattr(L, "hrfd_audio_create"):                    # (an older build named by HRFD_LIB has no audio bank)
         L.hrfd_audio_create.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]
         L.hrfd_audio_destroy.argtypes = [_vp]
@@ -234,6 +236,8 @@ def load() -> C.CDLL:
         L.hrfd_audio_gate_device.argtypes = [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]
         L.hrfd_audio_process.argtypes = [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]
         L.hrfd_audio_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]
+        if hasattr(L, "hrfd_audio_debug_set_max_wgs"):     # (an older build named by HRFD_LIB has none)
+            L.hrfd_audio_debug_set_max_wgs.argtypes = [_vp, C.c_uint32]
     if hasattr(L, "hrfd_resamp_create"):                   # (an older build named by HRFD_LIB has no resampler bank)
         L.hrfd_resamp_create.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]
         L.hrfd_resamp_destroy.argtypes = [_vp]
@@ -242,6 +246,8 @@ def load() -> C.CDLL:
         L.hrfd_resamp_out_count.argtypes = [_vp, C.c_uint32, _u32p]
         L.hrfd_resamp_process.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _u32p]
         L.hrfd_resamp_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, _u32p, _vp]
+        if hasattr(L, "hrfd_resamp_debug_set_max_wgs"):     # (an older build named by HRFD_LIB has none)
+            L.hrfd_resamp_debug_set_max_wgs.argtypes = [_vp, C.c_uint32]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

@@ -568,6 +568,15 @@ class _Bank:
     __del__ = close
 
 
+class _PcmBank(_Bank):
+    """What Tones, Audio and Resampler share beyond _Bank: their hot kernels go out through the chunked launch."""
+
+    def debug_set_max_wgs(self, n: int):
+        """test hook (needs HRFD_DEBUG_HOOKS=1): at most n workgroups per launch, 1..2^22 (the default), so that a small call
+        is cut into launches the way one of more than 2^22 workgroups is"""
+        self._call("debug_set_max_wgs", int(n))
+
+
 class _TunedBank(_Bank):
     """The calls of Ddc and Duc that differ in the prefix only."""
 
@@ -945,7 +954,7 @@ def dtmf_digit(low_best: int, high_best: int) -> str:
     return DTMF_KEYS[int(low_best)][int(high_best)]
 
 
-class Tones(_Bank):
+class Tones(_PcmBank):
     """A bank of tone detectors (hrfd_tone_*): the PCM of n_channels channels as Rx / Ddc.receive write it in, per frame of
     frame_len samples the power at every tone of one shared list, the frame's energy and a verdict per tone group out."""
 
@@ -1047,7 +1056,7 @@ def audio_highpass_taps(T: int = 511, cutoff_hz: float = 300.0) -> np.ndarray:
     return np.floor(h * 16384.0 + 0.5).astype(np.int16)
 
 
-class Audio(_Bank):
+class Audio(_PcmBank):
     """The audio bank (hrfd_audio_*): the PCM of n_channels channels as Rx / Ddc.receive write it in; every channel's audio
     behind one voice filter and a click-free per-block gate, and n_buses monitor mixes of it out.  gate / gate_device turn
     the verdicts of Tones into the gate (tone squelch)."""
@@ -1159,7 +1168,7 @@ def resample_taps(up: int, down: int, taps_per_branch: int, atten_db: float = No
     return np.floor(h * 16384.0 + 0.5).astype(np.int16)
 
 
-class Resampler(_Bank):
+class Resampler(_PcmBank):
     """The resampler bank (hrfd_resamp_*): the PCM of n_channels channels at up / down times its rate, the same rational
     polyphase filter for every channel: 8 kS/s to a sound card's 48 kS/s with (6, 1), a microphone's 48 kS/s to the
     modulators' 8 kS/s with (1, 6), 44.1 kS/s with (441, 80) and (80, 441).  Exact in integers and independent of how a stream

@@ -419,6 +419,13 @@ extern "C" int hrfd_audio_reset(hrfd_audio *a, uint32_t channel)
   return HRFD_OK;
 }
 
+// test hook: the workgroups of one launch of k_audio_fir, 1 .. 2^22 (2^22 unless set)
+extern "C" int hrfd_audio_debug_set_max_wgs(hrfd_audio *a, uint32_t n)
+{
+  HRFD_HOOK_GATE("hrfd_audio_debug_set_max_wgs");
+  return hrfd::bank_set_max_wgs("hrfd_audio_debug_set_max_wgs", a, n);
+}
+
 // the wanted tones, if a setter changed them; under core.mu, between staging_wait and staging_sent
 static int audio_send_want(hrfd_audio *a, hipStream_t st)
 {
@@ -550,7 +557,7 @@ static int audio_launch(hrfd_audio *a, const int16_t *d_pcm, uint64_t stride, co
   P.n_blocks = n_blocks;
   P.runs = (n_blocks + kAudioRun - 1) / kAudioRun;
   P.n_wgs = a->n_channels * P.runs;                        // <= 2^24
-  BANK_TRY(bank_launch_chunked("k_audio_fir", P.n_wgs, P, [&](dim3 grid) {
+  BANK_TRY(bank_launch_chunked("k_audio_fir", a->core, P.n_wgs, P, [&](dim3 grid) {
     hipLaunchKernelGGL(k_audio_fir, grid, dim3(kAudioThreads), 0, st, P, (const uint2 *)a->d_taps.p);
   }));
   if (d_mix != nullptr || d_clips != nullptr)

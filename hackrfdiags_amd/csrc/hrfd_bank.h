@@ -1,5 +1,6 @@
 // hackrfdiags_amd/csrc/hrfd_bank.h -- what the banks share and no HIP is needed for: BANK_TRY, the tuning record of the DDC
-// and the DUC and its phase law, the tap check and tap packing of every FIR, and the DUC's per-capture channel lists.
+// and the DUC and its phase law, the tap check and tap packing of every FIR, the cut of a call into launches
+// (bank_each_chunk), and the DUC's per-capture channel lists.
 // hrfd_pcm.h adds the PCM contract on top.  Plain C++ (tests/cpp/san_bank.cc compiles it on the CPU); the includer
 // declares `int fail(int code, const char *fmt, ...)` and the HRFD_* codes first.
 #pragma once
@@ -114,6 +115,35 @@ inline void bank_pack_branch_taps(const int16_t *h, int T, int R, Pair *out, int
     }
     bank_pack_taps(hp.data(), LA + 1, out + p * J, J);
   }
+}
+
+constexpr uint32_t kBankMaxWgs = 1u << 22; // workgroups of one launch
+static_assert((uint64_t)kBankMaxWgs * 256 <= (1ull << 30), "a launch of 256-thread workgroups stays at 2^30 work-items");
+
+// The launches of a call of n_wgs workgroups, at most max_wgs each: f(first, count) for every launch in order, contiguous
+// from 0 and none empty; n_wgs = 0 gives none.  First is the type the kernel's parameters hold `first` in: a call whose last
+// launch would start above its range is refused in front of the first launch, never truncated.  f answers HRFD_OK or the
+// failure that ends the call.
+template <class First, class F>
+inline int bank_each_chunk(const char *kernel, uint64_t n_wgs, uint32_t max_wgs, F f)
+{
+  if (max_wgs < 1 || max_wgs > kBankMaxWgs)
+  {
+    return fail(HRFD_EINVAL, "%s: %u workgroups per launch (1..%u)", kernel, max_wgs, kBankMaxWgs);
+  }
+  constexpr uint64_t top = (uint64_t)(First)~(First)0;
+  static_assert((First)~(First)0 > (First)0 && sizeof(First) <= 8, "first_wg is unsigned");
+  if (n_wgs > 0 && (n_wgs - 1) / max_wgs * max_wgs > top)
+  {
+    return fail(HRFD_EINVAL, "%s: %llu workgroups in launches of %u: the last launch starts above the %u bits of first_wg", kernel,
+                (unsigned long long)n_wgs, max_wgs, 8u * (uint32_t)sizeof(First));
+  }
+  for (uint64_t first = 0; first < n_wgs; first += max_wgs)
+  {
+    const uint64_t left = n_wgs - first;
+    BANK_TRY(f((First)first, (uint32_t)(left < max_wgs ? left : max_wgs)));
+  }
+  return HRFD_OK;
 }
 
 // the channels of every capture, in channel order (a counting sort): those of capture w are

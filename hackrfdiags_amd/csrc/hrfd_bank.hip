@@ -37,6 +37,7 @@ struct BankCore
   hipEvent_t ev_last = nullptr;            // recorded on last_stream when the next launch runs on another stream
   hipEvent_t ev_upload = nullptr;          // the last upload from the pinned staging buffers has been read
   std::mutex mu;                           // guards the handle's host records (setters may come from another thread)
+  uint32_t max_wgs = kBankMaxWgs;          // workgroups of one launch of a chunked call (bank_launch_chunked); under mu
 
   // `who` is the public create function.  Nothing is left open on failure.
   int open(const char *who, int dev)
@@ -134,18 +135,34 @@ static int bank_launch_ok(const char *kernel)
   return e == hipSuccess ? HRFD_OK : fail(HRFD_ENODEV, "%s launch failed: %s", kernel, hipGetErrorString(e));
 }
 
-constexpr uint32_t kBankMaxWgs = 1u << 22; // workgroups of one launch: 2^30 work-items of 256 threads
-
-// n_wgs workgroups in launches of at most kBankMaxWgs: launch(grid) starts one with P.first_wg set to its first workgroup
+// n_wgs workgroups in launches of at most core.max_wgs (bank_each_chunk cuts them): launch(grid) starts one with P.first_wg
+// set to its first workgroup
 template <class Params, class Launch>
-static int bank_launch_chunked(const char *kernel, uint64_t n_wgs, Params &P, Launch launch)
+static int bank_launch_chunked(const char *kernel, BankCore &core, uint64_t n_wgs, Params &P, Launch launch)
 {
-  for (uint64_t first = 0; first < n_wgs; first += kBankMaxWgs)
+  uint32_t max_wgs;
   {
-    P.first_wg = (decltype(P.first_wg))first;
-    launch(dim3((uint32_t)std::min<uint64_t>(kBankMaxWgs, n_wgs - first)));
-    BANK_TRY(bank_launch_ok(kernel));
+    std::lock_guard<std::mutex> g(core.mu);
+    max_wgs = core.max_wgs;
   }
+  return bank_each_chunk<decltype(P.first_wg)>(kernel, n_wgs, max_wgs, [&](decltype(P.first_wg) first, uint32_t count) {
+    P.first_wg = first;
+    launch(dim3(count));
+    return bank_launch_ok(kernel);
+  });
+}
+
+// test hook of the PCM banks (hrfd_<bank>_debug_set_max_wgs, behind HRFD_HOOK_GATE): with few workgroups per launch a small
+// call is cut the way one of more than kBankMaxWgs workgroups is
+template <class H>
+static int bank_set_max_wgs(const char *who, H *h, uint32_t n)
+{
+  if (h == nullptr || n < 1 || n > kBankMaxWgs)
+  {
+    return fail(HRFD_EINVAL, "%s: need a handle and 1..%u workgroups per launch (got %u)", who, kBankMaxWgs, n);
+  }
+  std::lock_guard<std::mutex> g(h->core.mu);
+  h->core.max_wgs = n;
   return HRFD_OK;
 }
 

@@ -293,6 +293,13 @@ extern "C" int hrfd_resamp_reset(hrfd_resamp *r, uint32_t channel)
   return HRFD_OK;
 }
 
+// test hook: the workgroups of one launch of k_resamp, 1 .. 2^22 (2^22 unless set)
+extern "C" int hrfd_resamp_debug_set_max_wgs(hrfd_resamp *r, uint32_t n)
+{
+  HRFD_HOOK_GATE("hrfd_resamp_debug_set_max_wgs");
+  return hrfd::bank_set_max_wgs("hrfd_resamp_debug_set_max_wgs", r, n);
+}
+
 extern "C" int hrfd_resamp_out_count(hrfd_resamp *r, uint32_t n_in, uint32_t *n_out)
 {
   using namespace hrfd;
@@ -392,7 +399,7 @@ static int resamp_launch(hrfd_resamp *r, const char *who, const int16_t *d_pcm, 
   P.M = r->M;
   P.Mq = r->M / r->L;
   P.Mr = r->M % r->L;
-  BANK_TRY(bank_launch_chunked("k_resamp", (uint64_t)r->n_channels * P.tiles, P, [&](dim3 grid) {
+  BANK_TRY(bank_launch_chunked("k_resamp", r->core, (uint64_t)r->n_channels * P.tiles, P, [&](dim3 grid) {
     hipLaunchKernelGGL(k_resamp, grid, dim3(kResampThreads), 0, st, P, (const uint32_t *)r->d_taps.p);
   }));
   r->core.launched_on(st);

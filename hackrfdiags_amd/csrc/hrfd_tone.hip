@@ -398,6 +398,13 @@ extern "C" int hrfd_tone_set_threshold(hrfd_tone *t, uint32_t group, uint32_t ra
   return HRFD_OK;
 }
 
+// test hook: the workgroups of one launch of k_tone, 1 .. 2^22 (2^22 unless set)
+extern "C" int hrfd_tone_debug_set_max_wgs(hrfd_tone *t, uint32_t n)
+{
+  HRFD_HOOK_GATE("hrfd_tone_debug_set_max_wgs");
+  return hrfd::bank_set_max_wgs("hrfd_tone_debug_set_max_wgs", t, n);
+}
+
 // the checks of both process entries; the tone count is read under the lock again at the launch
 static int tone_check_process(hrfd_tone *t, const char *who, const void *pcm, uint64_t stride, bool device_entry, uint32_t n_blocks,
                               const void *power, const void *energy, const void *valid, const void *best, const void *present)
@@ -460,7 +467,7 @@ static int tone_launch(hrfd_tone *t, const int16_t *d_pcm, uint64_t stride, cons
   P.F = kToneBlock * n_blocks / L;
   P.G = t->n_channels * P.F;
   const uint32_t FT = std::min((uint32_t)kToneMaxFrames, (uint32_t)kToneTile / L);
-  BANK_TRY(bank_launch_chunked("k_tone", (P.G + FT - 1) / FT, P, [&](dim3 grid) {
+  BANK_TRY(bank_launch_chunked("k_tone", t->core, (P.G + FT - 1) / FT, P, [&](dim3 grid) {
     const dim3 block(kToneThreads);
     switch (FT)
     {

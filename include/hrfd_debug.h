@@ -76,6 +76,12 @@ int hrfd_mod_debug_set_sliced(hrfd_mod *h, int on);      /* WBFM modulator: 0 un
 int hrfd_mod_debug_set_scan(hrfd_mod *h, int kind);      /* FM / WBFM modulators: the phase recurrence on 0 = k_phase_rows8 / k_phase_rows, 1 = k_phase_scan<64>, 2 = k_phase_rows */
 int hrfd_mod_debug_set_tail(hrfd_mod *h, int kind);      /* WBFM modulator: 0 = k_wb_rails + k_mod<WB_TAIL> (rounds 2-5), 1 = k_wb_tail (one pass) */
 int hrfd_cal_debug_set_workgroups(hrfd_cal *c, int wgs); /* conditioner: workgroups a launch aims for, 1 .. 65536 (2048 unless set); 1 = one per capture */
+/* tone, audio and resampler banks: the workgroups of one launch of k_tone / k_audio_fir / k_resamp, 1 .. 2^22 (2^22 unless
+ * set).  A call that needs more is cut into several launches, so a small n runs a small call the way a call of more than
+ * 2^22 workgroups runs (tests/test_gpu_chunked_launch.py) */
+int hrfd_tone_debug_set_max_wgs(hrfd_tone *t, uint32_t n);
+int hrfd_audio_debug_set_max_wgs(hrfd_audio *a, uint32_t n);
+int hrfd_resamp_debug_set_max_wgs(hrfd_resamp *r, uint32_t n);
 
 #ifdef __cplusplus
 }

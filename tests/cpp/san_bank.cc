@@ -90,8 +90,79 @@ static int check_taps(const std::vector<int16_t> &h, const std::vector<int16_t> 
   return 0;
 }
 
+// bank_each_chunk over (n_wgs, max_wgs) with `first` held in First: the launches are contiguous from 0, none is empty, none
+// exceeds max_wgs, they cover [0, n_wgs) exactly once and there are ceil(n_wgs / max_wgs) of them
+template <class First>
+static int check_chunks(uint64_t n_wgs, uint32_t max_wgs)
+{
+  uint64_t next = 0, launches = 0;
+  bool ok = true;
+  const int rc = bank_each_chunk<First>("t", n_wgs, max_wgs, [&](First first, uint32_t count) {
+    ok = ok && (uint64_t)first == next && count >= 1 && count <= max_wgs;
+    next += count;
+    launches++;
+    return HRFD_OK;
+  });
+  CHECK(rc == HRFD_OK && ok);
+  CHECK(next == n_wgs);
+  CHECK(launches == (n_wgs + max_wgs - 1) / max_wgs);
+  return 0;
+}
+
+// a call that bank_each_chunk must refuse, in front of the first launch
+template <class First>
+static int check_chunks_refused(uint64_t n_wgs, uint32_t max_wgs)
+{
+  uint64_t launches = 0;
+  const int rc = bank_each_chunk<First>("t", n_wgs, max_wgs, [&](First, uint32_t) {
+    launches++;
+    return HRFD_OK;
+  });
+  CHECK(rc == HRFD_EINVAL && launches == 0);
+  return 0;
+}
+
+static int check_chunking()
+{
+  const uint32_t max = kBankMaxWgs;
+  CHECK(max == (1u << 22));
+  const uint64_t m64 = max;
+  for (uint64_t n : std::vector<uint64_t>{0, 1, m64 - 1, m64, m64 + 1, 2 * m64, 2 * m64 + 1})
+  {
+    if (check_chunks<uint32_t>(n, max) != 0 || check_chunks<uint64_t>(n, max) != 0) return 1;
+  }
+  // 2^34 workgroups (the resampler's most): 4096 launches where first_wg has 64 bits; 32 bits cannot number a launch that
+  // starts at 2^32, so 2^32 workgroups (the last launch starts at 2^32 - 2^22) are the most they take
+  if (check_chunks<uint64_t>(1ull << 34, max) != 0 || check_chunks_refused<uint32_t>(1ull << 34, max) != 0) return 1;
+  if (check_chunks<uint32_t>(1ull << 32, max) != 0 || check_chunks_refused<uint32_t>((1ull << 32) + 1, max) != 0) return 1;
+  for (uint32_t m : {1u, 2u, 3u, 7u})
+  {
+    for (uint64_t n = 0; n <= 50; n++)
+    {
+      if (check_chunks<uint32_t>(n, m) != 0 || check_chunks<uint64_t>(n, m) != 0) return 1;
+    }
+  }
+  // a narrow first_wg at small sizes: 255 is the last start a byte holds
+  if (check_chunks<uint8_t>(256, 1) != 0 || check_chunks_refused<uint8_t>(257, 1) != 0) return 1;
+  if (check_chunks<uint8_t>(7 * 37, 7) != 0 || check_chunks_refused<uint8_t>(7 * 37 + 1, 7) != 0) return 1;      // 252 / 259
+  // n_wgs = 0 launches nothing whatever the limit; a limit outside 1 .. kBankMaxWgs is refused
+  if (check_chunks<uint32_t>(0, 1) != 0 || check_chunks_refused<uint32_t>(5, 0) != 0 || check_chunks_refused<uint64_t>(5, max + 1) != 0)
+    return 1;
+  // a launch that fails ends the call there, with its code
+  {
+    uint64_t launches = 0;
+    const int rc = bank_each_chunk<uint32_t>("t", 10, 3, [&](uint32_t, uint32_t) { return ++launches == 2 ? HRFD_ENODEV : HRFD_OK; });
+    CHECK(rc == HRFD_ENODEV && launches == 2);
+  }
+  return 0;
+}
+
 int main()
 {
+  if (check_chunking() != 0)
+  {
+    return 1;
+  }
   std::mt19937 rng(7);
   std::vector<int16_t> x(700);
   for (int16_t &v : x)

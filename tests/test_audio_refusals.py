@@ -174,3 +174,10 @@ def test_process_checks_sizes_and_addresses_before_the_handle(lib):
     refused(lib, dev, NULL, p, 1026, NULL, NULL, 1, q, 1030, NULL, NULL, NULL, word="NULL handle")
     refused(lib, dev, NULL, p, 1026, NULL, NULL, 1, q, 1030, NULL, q, NULL, word="NULL handle")
     refused(lib, host, NULL, p, NULL, NULL, 1, NULL, q, NULL, word="NULL handle")
+
+
+def test_the_max_wgs_hook_is_inert_without_the_opt_in():
+    """hrfd_audio_debug_set_max_wgs: HRFD_ESTATE naming HRFD_DEBUG_HOOKS in a process without the opt-in, whatever its
+    arguments; HRFD_EINVAL for the NULL handle in one with it (child processes: the library reads the variable once)"""
+    from tests.hooks import check_max_wgs_hook_refusals
+    check_max_wgs_hook_refusals("hrfd_audio_debug_set_max_wgs")

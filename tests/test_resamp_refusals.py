@@ -135,3 +135,10 @@ def test_process_checks_sizes_and_addresses_before_the_handle(lib):
         refused(lib, dev, NULL, C.c_void_p(a + res), 1030, p, 512, C.c_void_p(a + 65536 + 14 - res), 6150, 3072, r, NULL, word="NULL handle")
     refused(lib, dev, NULL, p, 2 * 524288, NULL, 524288, C.c_void_p(a + (1 << 21)), 2, 0, r, NULL, word="NULL handle")
     assert n.value == 0
+
+
+def test_the_max_wgs_hook_is_inert_without_the_opt_in():
+    """hrfd_resamp_debug_set_max_wgs: HRFD_ESTATE naming HRFD_DEBUG_HOOKS in a process without the opt-in, whatever its
+    arguments; HRFD_EINVAL for the NULL handle in one with it (child processes: the library reads the variable once)"""
+    from tests.hooks import check_max_wgs_hook_refusals
+    check_max_wgs_hook_refusals("hrfd_resamp_debug_set_max_wgs")

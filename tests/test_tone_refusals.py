@@ -130,3 +130,10 @@ def test_process_checks_sizes_and_addresses_before_the_handle(lib):
         outs[i] = q
         refused(lib, "hrfd_tone_process_device", NULL, p, 1026, NULL, 1, *outs, NULL, word="NULL handle")
         refused(lib, "hrfd_tone_process", NULL, p, NULL, 1, *outs, word="NULL handle")
+
+
+def test_the_max_wgs_hook_is_inert_without_the_opt_in():
+    """hrfd_tone_debug_set_max_wgs: HRFD_ESTATE naming HRFD_DEBUG_HOOKS in a process without the opt-in, whatever its
+    arguments; HRFD_EINVAL for the NULL handle in one with it (child processes: the library reads the variable once)"""
+    from tests.hooks import check_max_wgs_hook_refusals
+    check_max_wgs_hook_refusals("hrfd_tone_debug_set_max_wgs")
