@@ -248,6 +248,15 @@ def load() -> C.CDLL:
         L.hrfd_resamp_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, _u32p, _vp]
         if hasattr(L, "hrfd_resamp_debug_set_max_wgs"):     # (an older build named by HRFD_LIB has none)
             L.hrfd_resamp_debug_set_max_wgs.argtypes = [_vp, C.c_uint32]
+    if hasattr(L, "hrfd_level_create"):                    # (an older build named by HRFD_LIB has no level bank)
+        L.hrfd_level_create.argtypes = [C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_level_destroy.argtypes = [_vp]
+        L.hrfd_level_set_weights.argtypes = [_vp, C.POINTER(C.c_uint16), C.c_uint32]
+        L.hrfd_level_set.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.hrfd_level_set_bypass.argtypes = [_vp, C.c_uint32, C.c_int]
+        L.hrfd_level_reset.argtypes = [_vp, C.c_uint32]
+        L.hrfd_level_process.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]
+        L.hrfd_level_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

@@ -1221,6 +1221,89 @@ class Resampler(_PcmBank):
         return int(v.value)
 
 
+LEVEL_FRAME = 64
+LEVEL_MAX_WEIGHTS = 64
+LEVEL_MAX_BLOCKS = 1024
+LEVEL_UNITY = 32768                # w[0], and the largest weight
+LEVEL_FRAME_MS = 1000.0 * LEVEL_FRAME / TONE_FS
+
+
+def level_weights(hang_ms: float, release_ms: float, W: int = LEVEL_MAX_WEIGHTS) -> np.ndarray:
+    """W uint16 release weights in Q15 for Leveler.set_weights, one per frame of 8 ms: entry k weighs the peak of the frame
+    that lies 8 k ms back.  32768 while 8 k <= hang_ms, then 32768 exp(-(8 k - hang_ms) / release_ms), rounded; w[0] is
+    32768 whatever the arguments say.  A design aid on the host, not part of the bank's exact contract."""
+    W = int(W)
+    if W < 1 or W > LEVEL_MAX_WEIGHTS:
+        raise ValueError(f"W must be 1..{LEVEL_MAX_WEIGHTS}, got {W}")
+    if not (hang_ms >= 0.0 and release_ms > 0.0):
+        raise ValueError(f"need hang_ms >= 0 and release_ms > 0, got {hang_ms}, {release_ms}")
+    t = np.maximum(np.arange(W, dtype=np.float64) * LEVEL_FRAME_MS - float(hang_ms), 0.0)
+    w = np.floor(LEVEL_UNITY * np.exp(-t / float(release_ms)) + 0.5).astype(np.uint16)
+    w[0] = LEVEL_UNITY
+    return w
+
+
+class Leveler(_Bank):
+    """The level bank (hrfd_level_*): the PCM of n_channels channels as Rx / Ddc.receive write it in, the same audio at an even
+    loudness out: a per-channel automatic gain control with a peak detector per frame of 64 samples, a table of release
+    weights (hang, then decay) and a gain that attacks at the frame boundary and releases in a ramp.  Exact in integers,
+    |out| <= target always, independent of how a stream is cut into calls.  (Its kernel is one launch of one workgroup per
+    channel, so unlike Tones, Audio and Resampler it has no chunked launch and no debug_set_max_wgs.)"""
+
+    _prefix = "level"
+
+    def __init__(self, n_channels: int, device: int = -1):
+        self.n = int(n_channels)
+        self._create(self.n, device)
+
+    def set_weights(self, w):
+        """1..64 uint16 release weights in Q15, w[0] = 32768 and none above it, one table for every channel
+        (level_weights designs one); keeps the peaks"""
+        a = np.ascontiguousarray(w).ravel()
+        if a.size and (a.min() < 0 or a.max() > 65535):
+            raise ValueError("a weight must fit uint16")
+        a = a.astype(np.uint16)
+        self._call("set_weights", a.ctypes.data_as(C.POINTER(C.c_uint16)), a.size)
+
+    def set(self, target: int, floor: int, channel: int = ALL):
+        """the level the loudest sample of a frame is brought to (0..32767) and the envelope below which the gain stops
+        rising (16..32768: the largest gain is target / floor), of one channel or of all; keeps the peaks"""
+        self._call("set", int(channel), int(target), int(floor))
+
+    def set_bypass(self, on: bool, channel: int = ALL):
+        """pass one channel, or all, through unchanged; gain and peak are still reported"""
+        self._call("set_bypass", int(channel), 1 if on else 0)
+
+    def reset(self, channel: int = ALL):
+        """zero the peaks of one channel, or of all"""
+        self._call("reset", int(channel))
+
+    def process(self, pcm: np.ndarray, n_pcm=None, want_out: bool = True, want_gain: bool = True, want_peak: bool = True):
+        """pcm int16 [n_channels, n_blocks, 512], n_pcm uint32 [n_channels, n_blocks] or None -> (out int16 [n_channels,
+        n_blocks, 512] or None, gain uint32 [n_channels, 8 n_blocks] or None, peak uint16 [n_channels, 8 n_blocks] or None);
+        blocking"""
+        x = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.n, -1)
+        n_blocks = x.shape[1] // 512
+        if x.shape[1] != 512 * n_blocks:
+            raise ValueError(f"a channel's PCM must be whole blocks of 512 samples, got {x.shape[1]} samples")
+        npc = None if n_pcm is None else np.ascontiguousarray(n_pcm, dtype=np.uint32).reshape(self.n, n_blocks)
+        out = np.zeros((self.n, n_blocks, 512), dtype=np.int16) if want_out else None
+        gain = np.zeros((self.n, 8 * n_blocks), dtype=np.uint32) if want_gain else None
+        peak = np.zeros((self.n, 8 * n_blocks), dtype=np.uint16) if want_peak else None
+        self._call("process", _ptr(x), _ptr(npc), n_blocks, _ptr(out), _ptr(gain), _ptr(peak))
+        return out, gain, peak
+
+    def process_device(self, d_pcm, channel_stride: int, d_n_pcm, n_blocks: int, d_out=None, out_stride: int = 0, d_gain=None,
+                       d_peak=None, stream=None):
+        """device pointers (ints); d_n_pcm and any output may be None (not all three outputs); out_stride 0 = the input's
+        stride where d_out is d_pcm (in place), dense rows otherwise; asynchronous on stream (None = the handle's own)"""
+        if not out_stride:
+            in_place = d_out is not None and _ptr(d_out).value == _ptr(d_pcm).value
+            out_stride = int(channel_stride) if in_place else 1024 * int(n_blocks)
+        self._call("process_device", _ptr(d_pcm), int(channel_stride), _ptr(d_n_pcm), int(n_blocks), _ptr(d_out), int(out_stride),
+                   _ptr(d_gain), _ptr(d_peak), _ptr(stream))
+
+
 class Engine:
     """Factory with the interface tests/goldencheck.py expects."""
 

@@ -1,5 +1,5 @@
 // hackrfdiags_amd/csrc/hrfd_bank.hip -- the host core of the bank handles (hrfd_ddc, hrfd_duc, hrfd_spec, hrfd_cal,
-// hrfd_tone, hrfd_audio, hrfd_resamp): device and stream ownership with the three ordering rules (BankCore), what stands
+// hrfd_tone, hrfd_audio, hrfd_resamp, hrfd_level): device and stream ownership with the three ordering rules (BankCore), what stands
 // around every launch (the NULL-handle refusal, the launch check, the chunked launch, the loop over the selected channels),
 // the blocking host entry (BankHostCall), the history of the PCM banks (BankHistory), and the setters and argument checks
 // the DDC and the DUC share.  DESIGN.md 3.5a states the rules; hrfd_bank.h and hrfd_pcm.h hold the parts that need no HIP,
@@ -233,22 +233,25 @@ private:
 
 // The filter history of a PCM bank (hrfd_audio, hrfd_resamp): per channel the last 512 samples as the filter saw them, as
 // 256 packed pairs, in a ping-pong of two sides (a launch reads in() and writes out(), flip() turns them over), and the
-// channels that start from zeros with the next launch.  Host fields under the handle's core.mu.
+// channels that start from zeros with the next launch.  hrfd_level keeps its 64 frame peaks per channel the same way, in
+// rows of 32 dwords.  Host fields under the handle's core.mu.
 struct BankHistory
 {
-  static constexpr size_t kDw = 256;       // dwords per channel
+  static constexpr size_t kDw = 256;       // dwords per channel, unless alloc is told otherwise
   size_t C = 0;
+  size_t dw = kDw;
   std::vector<uint8_t> fresh;              // per channel
   bool any_fresh = false;
   uint32_t side = 0;                       // the side the next launch reads
-  DevBuf<uint32_t> d_hist;                 // [2][C][256]
+  DevBuf<uint32_t> d_hist;                 // [2][C][dw]
   DevBuf<uint8_t> d_fresh;                 // [C]
 
-  bool alloc(size_t n_channels)
+  bool alloc(size_t n_channels, size_t dwords = kDw)
   {
     C = n_channels;
+    dw = dwords;
     fresh.assign(C, 0);
-    return d_hist.alloc(2 * C * kDw) && d_fresh.alloc(C) && hipMemset(d_hist, 0, 4 * 2 * C * kDw) == hipSuccess;
+    return d_hist.alloc(2 * C * dw) && d_fresh.alloc(C) && hipMemset(d_hist, 0, 4 * 2 * C * dw) == hipSuccess;
   }
 
   void mark(uint32_t channel)
@@ -273,8 +276,8 @@ struct BankHistory
     return HRFD_OK;
   }
 
-  const uint32_t *in() const { return d_hist + side * C * kDw; }
-  uint32_t *out() const { return d_hist + (side ^ 1u) * C * kDw; }
+  const uint32_t *in() const { return d_hist + side * C * dw; }
+  uint32_t *out() const { return d_hist + (side ^ 1u) * C * dw; }
   void flip() { side ^= 1u; }
 };
 

@@ -793,6 +793,70 @@ int hrfd_resamp_process_device(hrfd_resamp *r, const int16_t *d_pcm, uint64_t ch
                                void *stream);
 
 /* ------------------------------------------------------------------------------
+ * Level bank: the PCM of C channels -> the same audio at an even loudness: a per-channel automatic gain control.  Behind a
+ * DDC bank the AM and SSB demodulators give PCM in proportion to each station's strength, and the radio's one hardware gain
+ * cannot even them out; this bank does, on the audio.  It reads what hrfd_rx_process_device / hrfd_ddc_receive write and the
+ * tone and audio banks read: PCM rows [C][n_blocks][512] int16 at 8 kS/s and, optionally, n_pcm [C][n_blocks].  Exact integer
+ * arithmetic with a law of its own, the same on every device and however a stream is cut into calls (tests/level_model.py
+ * restates it); shifts are arithmetic, the division is that of non-negative integers.  Everything is per channel; a frame
+ * is HRFD_LEVEL_FRAME = 64 samples (8 ms), a block 8 frames:
+ *   sizes     C = 1..65536 channels, fixed at create; W = 1..HRFD_LEVEL_MAX_WEIGHTS = 64 release weights, one table for
+ *             every channel; n_blocks = 1..HRFD_LEVEL_MAX_BLOCKS = 1024.
+ *   input     x[n] = the int16 sample, or 0 where n_pcm is given and the sample's position in its block is
+ *             >= min(n_pcm[c][b], 512): the tone bank's law.  The bytes there do not matter.
+ *   peak      p[f] = max |x| over frame f, 0..32768 (|-32768| = 32768).  Frames before the stream's start and after
+ *             hrfd_level_reset have p = 0.
+ *   envelope  E[f] = max(floor, max_{k=0..W-1} ((p[f-k] w[k] + 2^14) >> 15)).  w: Q15 weights with w[0] = 32768 (required:
+ *             E[f] >= p[f] rests on it) and every w[k] <= 32768.  A weighted sliding maximum: it rises within the frame and
+ *             falls as the table says (hang time, then decay); there is no recurrence.
+ *   gain      g[f] = (target << 12) / E[f], Q12.  target = 0..32767, floor = 16..32768, per channel: g <= 8388352 < 2^23,
+ *             and the largest gain is target / floor.
+ *   ramp      sample n = 0..63 of frame f has gs = g[f] where g[f] <= g[f-1] (attack takes effect at the frame boundary),
+ *             else g[f-1] + (((g[f] - g[f-1]) (n + 1)) >> 6) (release is ramped over the frame).  g[f-1] of a call's first
+ *             frame is recomputed by the gain rule from the 64 peaks before it under the settings of THIS call: the handle's
+ *             whole state is the last 64 peaks per channel.
+ *   output    y = (x gs + 2^11) >> 12.  |x| <= p[f] <= E[f] and gs <= g[f] give |x gs| <= target << 12 < 2^27, so
+ *             |y| <= target always: no saturation, no clip counter.
+ *   bypass    per channel: y = x (0 behind the block's limit); gain and peak are reported as if not bypassed.
+ *   defaults  target 8192, floor 64, no bypass; W = 64 with w[k] = 32768 for k < 8 and (32768 (64 - k)) / 56 from there: a
+ *             64 ms hang, then linear to the end of a 512 ms window.
+ * hrfd_level_set_weights and hrfd_level_set do not clear the peaks (they are facts about the signal); only hrfd_level_reset
+ * does.  Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well).  Setters never wait for the
+ * device: what a setter changed is copied to the device on the next call's stream, ahead of its launch.  Calls may use
+ * different streams: each launch is ordered on the device behind the handle's previous one (the peaks are the handle's), so
+ * a call chains behind the receive call that filled its input when both are given the same stream.
+ *   hrfd_level_set_weights     W weights, w[0] = 32768; keeps the peaks
+ *   hrfd_level_set             channel: 0..C-1 or HRFD_ALL_CHANNELS; keeps the peaks
+ *   hrfd_level_set_bypass      channel: 0..C-1 or HRFD_ALL_CHANNELS; on: 0 = levelled, anything else = bypassed
+ *   hrfd_level_reset           the peaks of one channel, or of all (HRFD_ALL_CHANNELS), from the next call on
+ *   hrfd_level_process         host buffers, dense: pcm [C][n_blocks][512], n_pcm [C][n_blocks] or NULL -> out
+ *                              [C][n_blocks][512] (y), gain uint32 [C][8 n_blocks] (g[f]), peak uint16 [C][8 n_blocks]
+ *                              (p[f]: a VU meter, and what a caller derives the tone bank's min_energy from); any output may
+ *                              be NULL, but not all three: without out the call is a meter.  out may be pcm itself; blocking
+ *   hrfd_level_process_device  device buffers; input rows channel_stride_bytes apart, rows of d_out out_stride_bytes apart
+ *                              (both even and >= 1024 n_blocks), d_pcm, d_out and d_peak at any even address, d_n_pcm and
+ *                              d_gain 4-byte aligned; d_gain and d_peak dense.  In place is allowed: d_out at exactly the
+ *                              input's address with the same stride, where every sample is read by the lane that overwrites
+ *                              it.  Any other overlap of d_out and the input is refused.  Asynchronous on `stream` (a
+ *                              hipStream_t, NULL = the handle's own)
+ */
+typedef struct hrfd_level hrfd_level;
+#define HRFD_LEVEL_FRAME 64
+#define HRFD_LEVEL_MAX_WEIGHTS 64
+#define HRFD_LEVEL_MAX_BLOCKS 1024
+int hrfd_level_create(uint32_t n_channels, int device, hrfd_level **out);
+int hrfd_level_destroy(hrfd_level *l);
+int hrfd_level_set_weights(hrfd_level *l, const uint16_t *w, uint32_t n);
+int hrfd_level_set(hrfd_level *l, uint32_t channel, uint32_t target, uint32_t floor);
+int hrfd_level_set_bypass(hrfd_level *l, uint32_t channel, int on);
+int hrfd_level_reset(hrfd_level *l, uint32_t channel);
+int hrfd_level_process(hrfd_level *l, const int16_t *pcm, const uint32_t *n_pcm, uint32_t n_blocks, int16_t *out, uint32_t *gain,
+                       uint16_t *peak);
+int hrfd_level_process_device(hrfd_level *l, const int16_t *d_pcm, uint64_t channel_stride_bytes, const uint32_t *d_n_pcm,
+                              uint32_t n_blocks, int16_t *d_out, uint64_t out_stride_bytes, uint32_t *d_gain, uint16_t *d_peak,
+                              void *stream);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",
