@@ -257,6 +257,19 @@ def load() -> C.CDLL:
         L.hrfd_level_reset.argtypes = [_vp, C.c_uint32]
         L.hrfd_level_process.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]
         L.hrfd_level_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]
+    if hasattr(L, "hrfd_tonegen_create"):                  # (an older build named by HRFD_LIB has no tone generator bank)
+        _u64p = C.POINTER(C.c_uint64)
+        L.hrfd_tonegen_create.argtypes = [C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_tonegen_destroy.argtypes = [_vp]
+        L.hrfd_tonegen_queue.argtypes = [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint64]
+        L.hrfd_tonegen_cut.argtypes = [_vp, C.c_uint32, C.c_uint32]
+        L.hrfd_tonegen_reset.argtypes = [_vp]
+        L.hrfd_tonegen_set_time.argtypes = [_vp, C.c_uint64]
+        L.hrfd_tonegen_time.argtypes = [_vp, _u64p]
+        L.hrfd_tonegen_pending.argtypes = [_vp, C.c_uint32, C.c_uint32, _u32p, _u64p]
+        L.hrfd_tonegen_get_clips.argtypes = [_vp, C.c_uint32, _u64p]
+        L.hrfd_tonegen_process.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp]
+        L.hrfd_tonegen_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

@@ -1304,6 +1304,150 @@ class Leveler(_Bank):
                    _ptr(d_gain), _ptr(d_peak), _ptr(stream))
 
 
+TONEGEN_TRACKS = 2
+TONEGEN_MAX_SEGMENTS = 32
+TONEGEN_MAX_BLOCKS = 1024
+TONEGEN_FOREVER = 0xFFFFFFFF
+TONEGEN_APPEND = 0xFFFFFFFFFFFFFFFF
+TONEGEN_RAMP = 64
+
+
+def tonegen_samples(ms: float) -> int:
+    """milliseconds at 8 kS/s in samples, rounded"""
+    return int(round(float(ms) * TONE_FS / 1000.0))
+
+
+def tonegen_segment(length: int, hz_a: float = 0.0, amp_a: int = 0, hz_b: float = 0.0, amp_b: int = 0, gap: int = 0):
+    """one segment for ToneGen.queue: (gap, length, step_a, step_b, amp_a, amp_b) with the steps of tone_step"""
+    return (int(gap), int(length), tone_step(hz_a), tone_step(hz_b), int(amp_a), int(amp_b))
+
+
+def tonegen_dtmf(key: str):
+    """(row Hz, column Hz) of a DTMF key"""
+    for r, row in enumerate(DTMF_KEYS):
+        if key in row and len(key) == 1:
+            return DTMF_LOW_HZ[r], DTMF_HIGH_HZ[row.index(key)]
+    raise ValueError(f"{key!r} is no DTMF key (one of {''.join(DTMF_KEYS)})")
+
+
+def _tonegen_segs(segs) -> np.ndarray:
+    try:
+        rows = [[int(v) for v in s] for s in segs]
+    except TypeError:
+        raise ValueError("segments are sequences of six integers (gap, length, step_a, step_b, amp_a, amp_b)")
+    if any(len(r) != 6 for r in rows) or any(v < 0 or v > 0xFFFFFFFF for r in rows for v in r):
+        raise ValueError("a segment is six values that fit uint32: gap, length, step_a, step_b, amp_a, amp_b")
+    return np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 6)
+
+
+class ToneGen(_Bank):
+    """The tone generator bank (hrfd_tonegen_*): signalling on the PCM of n_channels transmit channels, the mirror of Tones.
+    Segments of one or two sines with a ramp of 8 ms at either end are queued on two tracks per channel at absolute stream
+    times and added, saturating, to the rows Mod and Duc.transmit read: DTMF digits, CTCSS sub-tones, tone bursts, paging
+    sequences.  Exact in integers on the detector's phase grid, and independent of how a stream is cut into calls.  (Its
+    kernel is one launch of at most 2^22 workgroups, so it has no chunked launch and no debug_set_max_wgs.)"""
+
+    _prefix = "tonegen"
+
+    def __init__(self, n_channels: int, device: int = -1):
+        self.n = int(n_channels)
+        self._create(self.n, device)
+
+    def queue(self, channel: int, track: int, segs, start: int = TONEGEN_APPEND):
+        """1..32 segments (gap, length, step_a, step_b, amp_a, amp_b; tonegen_segment makes one) on one track of one channel
+        or of all (ALL): the first begins at start + its gap, each next one its gap behind the end of the one before; start
+        TONEGEN_APPEND = max(time, the end of the track's last segment).  Refused whole if anything is out of order."""
+        a = _tonegen_segs(segs)
+        self._call("queue", int(channel), int(track), _ptr(a), a.shape[0], int(start))
+
+    def cut(self, channel: int = ALL, track: int = 0):
+        """ramp the segment in progress down over the next 64 samples and drop those not yet begun"""
+        self._call("cut", int(channel), int(track))
+
+    def reset(self):
+        """empty every queue, time = 0, clips = 0"""
+        self._call("reset")
+
+    def set_time(self, N: int):
+        """move the clock only; the queues stay"""
+        self._call("set_time", int(N))
+
+    def time(self) -> int:
+        """the stream time of the next call's first sample"""
+        v = C.c_uint64(0)
+        self._call("time", C.byref(v))
+        return int(v.value)
+
+    def pending(self, channel: int, track: int = 0):
+        """(segments of the track that have not ended, the end of the last of them: the time itself where there is none,
+        2^64 - 1 behind a FOREVER segment)"""
+        n, end = C.c_uint32(0), C.c_uint64(0)
+        self._call("pending", int(channel), int(track), C.byref(n), C.byref(end))
+        return int(n.value), int(end.value)
+
+    def clips(self, channel: int) -> int:
+        """samples of the channel the saturation changed, since create or reset; blocking"""
+        v = C.c_uint64(0)
+        self._call("get_clips", int(channel), C.byref(v))
+        return int(v.value)
+
+    def process(self, pcm, n_blocks: int = None, want_active: bool = False):
+        """pcm int16 [n_channels, n_blocks, 512], or None with n_blocks (generate only) -> out int16 [n_channels, n_blocks,
+        512], or (out, active uint8 [n_channels, n_blocks]) with want_active; blocking"""
+        x = None
+        if pcm is not None:
+            x = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.n, -1)
+            if x.shape[1] % 512 != 0 or (n_blocks is not None and x.shape[1] != 512 * int(n_blocks)):
+                raise ValueError(f"a channel's PCM must be whole blocks of 512 samples, got {x.shape[1]} samples")
+            n_blocks = x.shape[1] // 512
+        elif n_blocks is None:
+            raise ValueError("generate only needs n_blocks")
+        n_blocks = int(n_blocks)
+        if n_blocks < 0 or n_blocks > 0xFFFFFFFF:
+            raise ValueError(f"n_blocks {n_blocks}")
+        out = np.zeros((self.n, min(n_blocks, TONEGEN_MAX_BLOCKS), 512), dtype=np.int16)
+        active = np.zeros((self.n, min(n_blocks, TONEGEN_MAX_BLOCKS)), dtype=np.uint8) if want_active else None
+        self._call("process", _ptr(x), n_blocks, _ptr(out), _ptr(active))
+        return (out, active) if want_active else out
+
+    def process_device(self, d_pcm, channel_stride: int, n_blocks: int, d_out, out_stride: int = 0, d_active=None, stream=None):
+        """device pointers (ints); d_pcm None = generate only, d_active may be None; out_stride 0 = the input's stride where
+        d_out is d_pcm (in place), dense rows otherwise; asynchronous on stream (None = the handle's own)"""
+        if not out_stride:
+            in_place = d_pcm is not None and d_out is not None and _ptr(d_out).value == _ptr(d_pcm).value
+            out_stride = int(channel_stride) if in_place else 1024 * int(n_blocks)
+        self._call("process_device", _ptr(d_pcm), int(channel_stride), int(n_blocks), _ptr(d_out), int(out_stride), _ptr(d_active),
+                   _ptr(stream))
+
+    # ---- what the segments are for
+    def dial(self, channel: int, keys: str, on_ms: float = 96, off_ms: float = 32, amplitude: int = 8000, track: int = 0,
+             start: int = TONEGEN_APPEND):
+        """DTMF: every key of `keys` (at most 32 with what the track still holds) for on_ms behind a pause of off_ms, row
+        and column at the same amplitude"""
+        on, off = tonegen_samples(on_ms), tonegen_samples(off_ms)
+        segs = []
+        for key in keys:
+            lo, hi = tonegen_dtmf(key)
+            segs.append(tonegen_segment(on, lo, amplitude, hi, amplitude, gap=off))
+        self.queue(channel, track, segs, start)
+
+    def ctcss(self, channel: int, hz: float, amplitude: int = 1000, track: int = 1, start: int = TONEGEN_APPEND):
+        """a sub-tone without an end (cut(channel, track) ramps it down)"""
+        self.queue(channel, track, [tonegen_segment(TONEGEN_FOREVER, hz, amplitude)], start)
+
+    def burst(self, channel: int, hz: float = 1750.0, ms: float = 500, amplitude: int = 8000, track: int = 0,
+              start: int = TONEGEN_APPEND):
+        """one tone for ms milliseconds: the 1750 Hz burst that opens a repeater"""
+        self.queue(channel, track, [tonegen_segment(tonegen_samples(ms), hz, amplitude)], start)
+
+    def tones(self, channel: int, hz_list, ms_each: float, amplitude: int = 8000, track: int = 0, gap_ms: float = 0,
+              start: int = TONEGEN_APPEND):
+        """sequential tones for paging and selcall, ms_each each, gap_ms of silence between; the caller brings the table"""
+        n, gap = tonegen_samples(ms_each), tonegen_samples(gap_ms)
+        segs = [tonegen_segment(n, hz, amplitude, gap=gap if i else 0) for i, hz in enumerate(hz_list)]
+        self.queue(channel, track, segs, start)
+
+
 class Engine:
     """Factory with the interface tests/goldencheck.py expects."""
 

@@ -857,6 +857,91 @@ int hrfd_level_process_device(hrfd_level *l, const int16_t *d_pcm, uint64_t chan
                               void *stream);
 
 /* ------------------------------------------------------------------------------
+ * Tone generator bank: signalling on the PCM of C transmit channels: CTCSS sub-tones, DTMF digits, tone bursts and paging
+ * sequences, added to the rows that hrfd_mod_* and hrfd_duc_transmit read.  The mirror of the tone bank: it sends on the
+ * detector's own phase grid.  PCM rows [C][n_blocks][512] int16 at 8 kS/s; there is no n_pcm (transmit PCM has none), and
+ * every sample of every block is written.  Exact integer arithmetic, the same on every device (tests/tonegen_model.py
+ * restates it); shifts are arithmetic.  Everything is per channel:
+ *   sizes     C = 1..65536 channels, fixed at create; n_blocks = 1..HRFD_TONEGEN_MAX_BLOCKS = 1024; HRFD_TONEGEN_TRACKS = 2
+ *             tracks per channel; at most HRFD_TONEGEN_MAX_SEGMENTS = 32 segments per track and channel that have not ended.
+ *   time      the handle keeps one uint64 sample counter N, the stream time of the next call's first sample.  Every call
+ *             advances it by 512 n_blocks, on the host.  Every stream time stays below 2^63.
+ *   segment   {gap, length, step_a, step_b, amp_a, amp_b}, six uint32, with a start s (uint64 stream time).  step =
+ *             round(f / 8000 * 2^32), the tone bank's; amp = 0..32767; length = 1..2^32-2 samples, or HRFD_TONEGEN_FOREVER =
+ *             0xFFFFFFFF: no end.  On one track segments never overlap; segments on different tracks may.
+ *   law       of one segment at stream time n, k = n - s, 0 <= k < length:
+ *               theta_x = (step_x k) mod 2^32             (only the low 32 bits of k matter)
+ *               i_x = ((theta_x + 2^19) >> 20) & 4095
+ *               S_x = COS[(i_x - 1024) & 4095]            (COS: "DDC_COS"; the tone bank's sine index: every segment starts at
+ *                                                          a zero crossing)
+ *               v = (amp_a S_a + amp_b S_b + 2^14) >> 15  (fits int32: 2 x 32767^2 + 2^14 < 2^31)
+ *               e = min(k + 1, length - k, 64)            (FOREVER: min(k + 1, 64))
+ *               g = (v e + 32) >> 6
+ *             a linear ramp of 64 samples (8 ms) at both ends, g = v between them.
+ *   output    y = sat16(x + g_track0 + g_track1); x is the input sample, or 0 when the call has no input (generate only).
+ *             clips[c] counts the samples where the saturation changed the value, until hrfd_tonegen_reset.
+ *   active    optional uint8 [C][n_blocks]: bit t is set when a segment of track t overlaps the block.  A caller keys a
+ *             transmitter with it.
+ * The output at stream time n is a pure function of n, the queue and x: however a stream is cut into calls, it comes out the
+ * same.  Segments that have ended (end <= N) leave the queue with the next call, hrfd_tonegen_queue or hrfd_tonegen_cut.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well).  No setter waits for the device:
+ * what changed is copied to the device on the next call's stream, ahead of its launch, and a call that already runs keeps the
+ * queue it was launched with.  Calls may use different streams: each launch is ordered on the device behind the handle's
+ * previous one.
+ *   hrfd_tonegen_queue          n = 1..32 segments on one track of one channel, or of all (HRFD_ALL_CHANNELS).  The first begins
+ *                               at start + segs[0].gap, each next one gap behind the end of the one before.  start =
+ *                               HRFD_TONEGEN_APPEND: max(N, the end of the track's last segment), per channel.  Segments may
+ *                               be queued in front of or between those already there.  Refused whole (HRFD_EINVAL, nothing
+ *                               queued on any channel): a start before N, an overlap on the track, anything behind a FOREVER
+ *                               segment, more than 32 segments that have not ended, an amp above 32767, a length of 0, a
+ *                               time at or above 2^63
+ *   hrfd_tonegen_cut            one track of one channel, or of all: the segment in progress at N (s <= N < end) is trimmed
+ *                               to end at min(its end, N + 64), which under the law is a ramp down; those not yet begun are
+ *                               dropped
+ *   hrfd_tonegen_reset          empties every queue, N = 0, clips = 0
+ *   hrfd_tonegen_set_time       moves the clock only: the queues stay (a segment the clock jumps into goes on at its k)
+ *   hrfd_tonegen_time           N
+ *   hrfd_tonegen_pending        of one track of one channel: the segments that have not ended at N, and the end of the last
+ *                               of them (N where there is none, UINT64_MAX behind a FOREVER segment); either result may be
+ *                               NULL, not both
+ *   hrfd_tonegen_get_clips      clips[channel]; blocks until the handle's calls have run
+ *   hrfd_tonegen_process        host buffers, dense: pcm [C][n_blocks][512] or NULL (generate only) -> out [C][n_blocks][512],
+ *                               active [C][n_blocks] or NULL.  out may be pcm itself; blocking
+ *   hrfd_tonegen_process_device device buffers; input rows channel_stride_bytes apart, rows of d_out out_stride_bytes apart
+ *                               (both even and >= 1024 n_blocks), d_pcm and d_out at any even address, d_active dense.  d_pcm
+ *                               may be NULL (generate only; its stride is not looked at).  In place is allowed: d_out at exactly
+ *                               the input's address with the same stride; a block no segment touches is then neither read
+ *                               nor written.  Any other overlap of d_out and the input is refused.  Asynchronous on `stream`
+ *                               (a hipStream_t, NULL = the handle's own)
+ */
+typedef struct hrfd_tonegen hrfd_tonegen;
+typedef struct hrfd_tonegen_segment
+{
+  uint32_t gap;                            /* samples of silence in front of the segment */
+  uint32_t length;                         /* samples, or HRFD_TONEGEN_FOREVER */
+  uint32_t step_a, step_b;
+  uint32_t amp_a, amp_b;
+} hrfd_tonegen_segment;
+#define HRFD_TONEGEN_TRACKS 2
+#define HRFD_TONEGEN_MAX_SEGMENTS 32
+#define HRFD_TONEGEN_MAX_BLOCKS 1024
+#define HRFD_TONEGEN_FOREVER 0xffffffffu
+#define HRFD_TONEGEN_APPEND UINT64_MAX
+int hrfd_tonegen_create(uint32_t n_channels, int device, hrfd_tonegen **out);
+int hrfd_tonegen_destroy(hrfd_tonegen *t);
+int hrfd_tonegen_queue(hrfd_tonegen *t, uint32_t channel, uint32_t track, const hrfd_tonegen_segment *segs, uint32_t n,
+                       uint64_t start);
+int hrfd_tonegen_cut(hrfd_tonegen *t, uint32_t channel, uint32_t track);
+int hrfd_tonegen_reset(hrfd_tonegen *t);
+int hrfd_tonegen_set_time(hrfd_tonegen *t, uint64_t N);
+int hrfd_tonegen_time(hrfd_tonegen *t, uint64_t *N);
+int hrfd_tonegen_pending(hrfd_tonegen *t, uint32_t channel, uint32_t track, uint32_t *n_segments, uint64_t *end);
+int hrfd_tonegen_get_clips(hrfd_tonegen *t, uint32_t channel, uint64_t *n);
+int hrfd_tonegen_process(hrfd_tonegen *t, const int16_t *pcm, uint32_t n_blocks, int16_t *out, uint8_t *active);
+int hrfd_tonegen_process_device(hrfd_tonegen *t, const int16_t *d_pcm, uint64_t channel_stride_bytes, uint32_t n_blocks,
+                                int16_t *d_out, uint64_t out_stride_bytes, uint8_t *d_active, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",
