@@ -309,7 +309,9 @@ def test_sixteen_captures_by_64_channels_at_r8(torch_dev):
     cap = lcg_captures(W, R * FULL, 77)
     dcap = torch.from_numpy(cap).to(dev)
     dout = torch.zeros((C, FULL), dtype=torch.int8, device=dev)
-    stream = torch.cuda.current_stream()
+    # a stream of the caller's.  (torch's default stream has the handle 0, which this entry reads as "the handle's own":
+    # a non-blocking stream that synchronising the default stream does not wait for, so the copy back raced the kernel)
+    stream = torch.cuda.Stream()
     torch.cuda.synchronize()
     d.process_device(dcap.data_ptr(), R * FULL, FULL, dout.data_ptr(), FULL, stream.cuda_stream)
     stream.synchronize()

@@ -45,6 +45,7 @@ GROUPS = [
     ("ingest_edges", "test_gpu_ingest_edges", "", 30),
     ("fanout_edges", "test_gpu_fanout_edges", "", 7),
     ("play_edges", "test_gpu_play_edges", "", 7),
+    ("bank_launch_shapes", "test_gpu_bank_launch_shapes", "", 41),      # all but the two under debug_set_workgroups
 ]
 
 
