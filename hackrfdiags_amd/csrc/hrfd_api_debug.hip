@@ -437,6 +437,7 @@ extern "C" int hrfd_mod_debug_set_sliced(hrfd_mod *h, int on)
   {
     return fail(HRFD_EINVAL, "NULL");
   }
+  std::lock_guard<std::mutex> g(h->core.mu);
   h->sliced = on;                                          // 0 off, 1 when the recurrence's stream has CUs of its own, 2 always
   return HRFD_OK;
 }
@@ -449,6 +450,7 @@ extern "C" int hrfd_mod_debug_set_scan(hrfd_mod *h, int kind)
   {
     return fail(HRFD_EINVAL, "hrfd_mod_debug_set_scan: kind 0 | 1 | 2");
   }
+  std::lock_guard<std::mutex> g(h->core.mu);
   h->scan_kind = kind;                                      // (2, round 6: k_phase_rows -- four steps per lane -- where k_phase_rows8 would run)
   return HRFD_OK;
 }
@@ -461,6 +463,7 @@ extern "C" int hrfd_mod_debug_set_tail(hrfd_mod *h, int kind)
   {
     return fail(HRFD_EINVAL, "hrfd_mod_debug_set_tail: kind 0 | 1");
   }
+  std::lock_guard<std::mutex> g(h->core.mu);
   h->wb_fused = kind;
   return HRFD_OK;
 }

@@ -1,6 +1,6 @@
 // hackrfdiags_amd/csrc/hrfd_buf.h -- device and pinned buffers a handle owns: freed with the handle, whatever members it
-// has (hrfd_rx, hrfd_mod, hrfd_nco and the bank handles).  Part of the unity translation unit hrfd_lib.hip, behind the
-// error helpers of hrfd_api.hip (fail).
+// has (hrfd_rx, and hrfd_mod, hrfd_nco and the bank handles on BankCore, hrfd_bank.hip).  Part of the unity translation
+// unit hrfd_lib.hip, behind the error helpers of hrfd_api.hip (fail).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

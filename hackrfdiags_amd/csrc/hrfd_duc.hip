@@ -658,9 +658,9 @@ extern "C" int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pc
   }
   const uint32_t in_bytes = 512u * n_per_channel;
   BANK_TRY(duc_check_call(d, d_pcm, in_bytes, in_bytes, d_captures, capture_stride, "hrfd_duc_transmit"));
-  if (mod->device != d->core.device)
+  if (mod->core.device != d->core.device)
   {
-    return fail(HRFD_EINVAL, "hrfd_duc_transmit: the modulator lives on device %d, the DUC on %d", mod->device,
+    return fail(HRFD_EINVAL, "hrfd_duc_transmit: the modulator lives on device %d, the DUC on %d", mod->core.device,
                 d->core.device);
   }
   HIP_TRY(hipSetDevice(d->core.device));

@@ -301,7 +301,13 @@ int hrfd_mod_set_modulation_index(hrfd_mod *h, uint32_t channel, float index);
 int hrfd_mod_set_deviation(hrfd_mod *h, uint32_t channel, float deviation_hz);
 /* pcm [n_channels][n_per_channel] int16 (SSB) or [n_channels][2*n_per_channel]
  * int16 IQ pairs (INTERP); iq_out [n_channels][512*n_per_channel] int8;
- * *out_bytes = 512*n_per_channel (bytes per channel, as the reference returns). */
+ * *out_bytes = 512*n_per_channel (bytes per channel, as the reference returns).
+ * hrfd_mod_process_device takes device buffers and is asynchronous on `stream` (a hipStream_t, NULL = the handle's own);
+ * hrfd_mod_sync waits for the handle's last launch.  Setters never wait for the device: what a setter changed goes to
+ * the device with the next call, ahead of its launch.  Calls may use different streams: each launch is ordered on the
+ * device behind the handle's previous one (the pipelines and phase accumulators are the handle's).  A call whose size
+ * does not fit the launches' 32-bit arithmetic -- 8 ceil(n_channels / 8) * ceil(n_per_channel / 128) above 2^24 - 1, or
+ * for HRFD_MOD_WBFM n_per_channel above 67108735 -- is refused with HRFD_EINVAL before any device is touched. */
 int hrfd_mod_process(hrfd_mod *h, const int16_t *pcm, uint32_t n_per_channel,
                      int8_t *iq_out, uint32_t *out_bytes);
 int hrfd_mod_process_device(hrfd_mod *h, const int16_t *d_pcm, uint32_t n_per_channel,
