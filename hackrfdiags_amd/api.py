@@ -1448,6 +1448,125 @@ class ToneGen(_Bank):
         self.queue(channel, track, segs, start)
 
 
+AFSK_MAX_WINDOW = 32
+AFSK_MAX_BLOCKS = 1024
+AFSK_BIT = 1                       # of a byte of bits: the value
+AFSK_CARRIER = 2                   # of a byte of bits: the carrier flag
+
+
+def afsk_step(hz: float) -> int:
+    """a tone's or a baud rate's phase step at 8 kS/s: round(f / 8000 * 2^32), not reduced (4000 gives 2^31)"""
+    return int(round(float(hz) / TONE_FS * 2.0 ** 32))
+
+
+def afsk_max_bits(baud_step: int, loop_shift: int, n_blocks: int) -> int:
+    """the most bits a call of n_blocks gives: ((512 n_blocks (baud_step + (2^31 >> A))) >> 32) + 1"""
+    return ((512 * int(n_blocks) * (int(baud_step) + ((1 << 31) >> int(loop_shift)))) >> 32) + 1
+
+
+def crc16_x25(data) -> int:
+    """CRC-16/X.25 (the frame check sequence of HDLC and AX.25): reflected 0x1021, start 0xFFFF, inverted"""
+    crc = 0xFFFF
+    for byte in bytes(data):
+        crc ^= byte
+        for _ in range(8):
+            crc = (crc >> 1) ^ 0x8408 if crc & 1 else crc >> 1
+    return crc ^ 0xFFFF
+
+
+def hdlc_frames(bits, min_payload: int = 1):
+    """the payloads of the HDLC frames in one channel's bit stream (Afsk's bits: only bit 0 of a byte counts), host only:
+    frames lie between 0x7E flags, a zero behind five ones is a stuffed one and is dropped, seven ones abort, bytes come
+    LSB first, and the last two are the CRC-16/X.25 of the rest, low byte first.  Returns the payloads (bytes, without the
+    check sequence) of the frames whose check sequence is good, in order.  Pass the streams of successive calls joined: a
+    frame may span calls."""
+    frames, cur, ones = [], None, 0
+    for v in (np.asarray(bits, dtype=np.uint8).ravel() & 1).tolist():
+        if v:
+            ones += 1
+            if cur is not None:
+                cur.append(1)
+            if ones >= 7:
+                cur = None
+            continue
+        if ones == 6:                                      # a flag: its 0 and six 1s are the last seven bits taken
+            if cur is not None and len(cur) >= 7 + 8 * (int(min_payload) + 2) and (len(cur) - 7) % 8 == 0:
+                data = np.packbits(np.array(cur[:-7], dtype=np.uint8), bitorder="little").tobytes()
+                if crc16_x25(data[:-2]) == data[-2] | (data[-1] << 8):
+                    frames.append(data[:-2])
+            cur = []
+        elif ones != 5 and cur is not None:                # (behind five ones: a stuffed zero)
+            cur.append(0)
+        ones = 0
+    return frames
+
+
+class Afsk(_Bank):
+    """The AFSK bank (hrfd_afsk_*): the PCM of n_channels channels as Rx / Ddc.receive write it in, the packet data on them
+    out: per channel the bits a recovered clock samples off a mark / space discriminator (Bell 202 by default), each with a
+    carrier flag, and optionally the discriminator's decision for every sample.  One modem for all channels.  Exact in
+    integers, independent of how a stream is cut into calls.  hdlc_frames turns a channel's bits into frames.  (Its kernel is
+    one launch of one workgroup per channel, so like Leveler it has no chunked launch and no debug_set_max_wgs.)"""
+
+    _prefix = "afsk"
+
+    def __init__(self, n_channels: int, mark_hz: float = 1200, space_hz: float = 2200, baud: float = 1200, window: int = 8,
+                 loop_shift: int = 2, nrzi: bool = True, device: int = 0):
+        self.n = int(n_channels)
+        self._create(self.n, device)
+        self.set_modem(mark_hz, space_hz, baud, window, loop_shift, nrzi)
+
+    def set_modem(self, mark_hz: float = 1200, space_hz: float = 2200, baud: float = 1200, window: int = 8, loop_shift: int = 2,
+                  nrzi: bool = True, steps=None):
+        """the modem of every channel (steps = (mark_step, space_step, baud_step) overrides the three rates); resets every
+        channel"""
+        m, s, b = (int(v) for v in steps) if steps is not None else (afsk_step(mark_hz), afsk_step(space_hz), afsk_step(baud))
+        for name, v in (("mark_step", m), ("space_step", s), ("baud_step", b), ("window", window), ("loop_shift", loop_shift)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} must fit uint32, got {v}")
+        self._call("set_modem", m, s, b, int(window), int(loop_shift), 1 if nrzi else 0)
+        self.baud_step, self.loop_shift = b, int(loop_shift)
+
+    def set_carrier(self, min_power: int):
+        """the carrier flag is set where P_mark + P_space > min_power (0..2^64-1; 0 unless set)"""
+        self._call("set_carrier", int(min_power))
+
+    def reset(self, channel: int = ALL):
+        """zero the state of one channel, or of all"""
+        self._call("reset", int(channel))
+
+    def max_bits(self, n_blocks: int) -> int:
+        """the most bits a call of n_blocks gives a channel: the least length of a row of bits"""
+        v = C.c_uint32(0)
+        self._call("max_bits", int(n_blocks), C.byref(v))
+        return int(v.value)
+
+    def process(self, pcm: np.ndarray, n_pcm=None, want_bits: bool = True, want_hard: bool = False):
+        """pcm int16 [n_channels, n_blocks, 512], n_pcm uint32 [n_channels, n_blocks] or None -> (bits: a list of n_channels
+        uint8 arrays, one byte per bit: AFSK_BIT | AFSK_CARRIER; or None, hard uint8 [n_channels, n_blocks, 64] or None);
+        blocking"""
+        x = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.n, -1)
+        n_blocks = x.shape[1] // 512
+        if x.shape[1] != 512 * n_blocks:
+            raise ValueError(f"a channel's PCM must be whole blocks of 512 samples, got {x.shape[1]} samples")
+        npc = None if n_pcm is None else np.ascontiguousarray(n_pcm, dtype=np.uint32).reshape(self.n, n_blocks)
+        rows = np.zeros((self.n, self.max_bits(n_blocks)), dtype=np.uint8) if want_bits else None
+        n_bits = np.zeros(self.n, dtype=np.uint32) if want_bits else None
+        hard = np.zeros((self.n, n_blocks, 64), dtype=np.uint8) if want_hard else None
+        self._call("process", _ptr(x), _ptr(npc), n_blocks, _ptr(rows), _ptr(n_bits), _ptr(hard))
+        bits = [rows[c, :n_bits[c]].copy() for c in range(self.n)] if want_bits else None
+        return bits, hard
+
+    def process_device(self, d_pcm, channel_stride: int, d_n_pcm, n_blocks: int, d_bits=None, bits_stride: int = 0, d_n_bits=None,
+                       d_hard=None, stream=None):
+        """device pointers (ints); d_n_pcm, d_hard, or d_bits with d_n_bits may be None (not all outputs); bits_stride 0 =
+        rows of max_bits(n_blocks) bytes; asynchronous on stream (None = the handle's own)"""
+        if not bits_stride and d_bits is not None:
+            bits_stride = self.max_bits(n_blocks)
+        self._call("process_device", _ptr(d_pcm), int(channel_stride), _ptr(d_n_pcm), int(n_blocks), _ptr(d_bits), int(bits_stride),
+                   _ptr(d_n_bits), _ptr(d_hard), _ptr(stream))
+
+
 class Engine:
     """Factory with the interface tests/goldencheck.py expects."""
 

@@ -948,6 +948,73 @@ int hrfd_tonegen_process_device(hrfd_tonegen *t, const int16_t *d_pcm, uint64_t 
                                 int16_t *d_out, uint64_t out_stride_bytes, uint8_t *d_active, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * AFSK bank: the PCM of C channels -> the packet data on them: audio frequency-shift keying, Bell 202 at 1200 baud (AX.25 /
+ * APRS, MDC-1200) and Bell 103 at 300 baud among it.  A matched filter per tone and sample, a hard decision, and a bit clock
+ * recovered from the decisions' transitions.  It reads what hrfd_rx_process_device / hrfd_ddc_receive write: PCM rows
+ * [C][n_blocks][512] int16 at 8 kS/s and, optionally, n_pcm [C][n_blocks].  Exact integer arithmetic with a law of its own,
+ * the same on every device and however a stream is cut into calls (tests/afsk_model.py restates it); shifts are arithmetic.
+ * One modem for every channel of a handle; everything else is per channel:
+ *   sizes     C = 1..65536 channels, fixed at create; n_blocks = 1..HRFD_AFSK_MAX_BLOCKS = 1024.
+ *   modem     mark_step, space_step = round(f / 8000 * 2^32), the tone bank's, 1..2^31; baud_step = round(baud / 8000 * 2^32),
+ *             1..2^31: at most one bit per sample; a window of W = 2..HRFD_AFSK_MAX_WINDOW = 32 samples; a loop shift
+ *             A = 1..8; nrzi on or off.
+ *   taps      for tone t in {mark, space} and k = 0..W-1: i = (((step_t k) mod 2^32 + 2^19) >> 20) & 4095,
+ *             C_t[k] = clamp((COS[i] + 8) >> 4, -2047, 2047), S_t[k] the same from COS[(i - 1024) & 4095]  (COS: "DDC_COS").
+ *   input     x[n] = the int16 sample, or 0 where n_pcm is given and the sample's position in its block is
+ *             >= min(n_pcm[c][b], 512): the tone bank's law, time runs on.  Samples before the stream's start or a reset are 0.
+ *   filter    I_t[n] = sum_k x[n-k] C_t[k], Q_t[n] the same with S_t.  |I| <= 32 x 32768 x 2047 < 2^31: every partial sum
+ *             fits an int32.  P_t = I_t^2 + Q_t^2 < 2^63, in 64 bits; d[n] = P_mark - P_space (int64); h[n] = d[n] > 0.
+ *   clock     a uint32 phase phi and the previous decision, both 0 at start.  For every sample, in this order:
+ *               1. new = (phi + baud_step) mod 2^32
+ *               2. if new < phi, a bit is sampled (below)
+ *               3. if h[n] != h[n-1]: new -= ((int32)(new - 2^31)) >> A.  This pulls the transition towards mid-bit; it
+ *                  never crosses 0 and never moves past 2^31
+ *               4. phi = new
+ *   bit       the sampled value is h[n]; with nrzi it is 1 - (h[n] ^ last), and then last = h[n] (last = 0 at start).  The
+ *             output byte carries the value in bit 0 and the carrier flag in bit 1: P_mark[n] + P_space[n] > min_power
+ *             (uint64, 0 unless set: digital silence carries no flag).
+ *   outputs   bits: uint8, one row per channel; n_bits uint32 [C]: this call's count; bytes of a row from n_bits[c] on are
+ *             not written.  A row holds at most hrfd_afsk_max_bits = ((512 n_blocks (baud_step + (2^31 >> A))) >> 32) + 1
+ *             bits, because the phase advances by at most that much per sample.  hard (optional): uint8 [C][n_blocks][64],
+ *             bit n & 7 of byte n >> 3 = h[n]: the discriminator's decisions, for a caller with a clock recovery of their own.
+ *             bits and n_bits go together, both or neither; hard may be NULL, but not all three.  A call without bits does
+ *             not run the clock: phi and last stay as they are, the samples and h[n-1] move on.
+ *   state     per channel the last W - 1 samples, phi, h[n-1] and last: 18 dwords.
+ *   defaults  1200 Hz mark, 2200 Hz space, 1200 baud, W = 8, A = 2, nrzi on; min_power 0.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well).  Setters never wait for the
+ * device: what a setter changed goes to the device with the next call, ahead of its launch.  Calls may use different
+ * streams: each launch is ordered on the device behind the handle's previous one (the state is the handle's), so a call
+ * chains behind the receive call that filled its input when both are given the same stream.
+ *   hrfd_afsk_set_modem        resets every channel: a history of another window length means nothing
+ *   hrfd_afsk_set_carrier      min_power, for every channel; keeps the state
+ *   hrfd_afsk_reset            the state of one channel, or of all (HRFD_ALL_CHANNELS), from the next call on
+ *   hrfd_afsk_max_bits         the bound above for n_blocks under the handle's modem
+ *   hrfd_afsk_process          host buffers, dense: pcm [C][n_blocks][512], n_pcm [C][n_blocks] or NULL -> bits
+ *                              [C][hrfd_afsk_max_bits], n_bits [C], hard [C][n_blocks][64]; blocking
+ *   hrfd_afsk_process_device   device buffers; input rows channel_stride_bytes apart (even and >= 1024 n_blocks), d_pcm at
+ *                              any even address, d_n_pcm and d_n_bits 4-byte aligned; rows of d_bits bits_stride_bytes
+ *                              apart, at least hrfd_afsk_max_bits (a smaller stride is refused); d_n_bits and d_hard dense.
+ *                              Asynchronous on `stream` (a hipStream_t, NULL = the handle's own)
+ */
+typedef struct hrfd_afsk hrfd_afsk;
+#define HRFD_AFSK_MAX_WINDOW 32
+#define HRFD_AFSK_MAX_BLOCKS 1024
+#define HRFD_AFSK_BIT 1u                   /* of a byte of bits: the value */
+#define HRFD_AFSK_CARRIER 2u               /* of a byte of bits: the carrier flag */
+int hrfd_afsk_create(uint32_t n_channels, int device, hrfd_afsk **out);
+int hrfd_afsk_destroy(hrfd_afsk *a);
+int hrfd_afsk_set_modem(hrfd_afsk *a, uint32_t mark_step, uint32_t space_step, uint32_t baud_step, uint32_t window,
+                        uint32_t loop_shift, int nrzi);
+int hrfd_afsk_set_carrier(hrfd_afsk *a, uint64_t min_power);
+int hrfd_afsk_reset(hrfd_afsk *a, uint32_t channel);
+int hrfd_afsk_max_bits(hrfd_afsk *a, uint32_t n_blocks, uint32_t *max_bits);
+int hrfd_afsk_process(hrfd_afsk *a, const int16_t *pcm, const uint32_t *n_pcm, uint32_t n_blocks, uint8_t *bits, uint32_t *n_bits,
+                      uint8_t *hard);
+int hrfd_afsk_process_device(hrfd_afsk *a, const int16_t *d_pcm, uint64_t channel_stride_bytes, const uint32_t *d_n_pcm,
+                             uint32_t n_blocks, uint8_t *d_bits, uint64_t bits_stride_bytes, uint32_t *d_n_bits, uint8_t *d_hard,
+                             void *stream);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",

@@ -63,6 +63,17 @@ int hrfd_debug_sincosf_digest(int variant, int form, uint32_t first_chunk, uint3
  * as the measured denominators beside the 8 TB/s spec peak (`measured_stream_read_GBps` / `_write_GBps`). */
 int hrfd_debug_membw(int kind, void *d_buf, size_t bytes, void *d_sink, void *stream);
 
+/* the AFSK bank's laws as the host states them (hrfd_afsk.h), no device needed; host pointers.
+ *   taps: out128 = [4][32] int16: the mark tone's cosine and sine taps, then the space tone's, zero from `window` on.
+ *   slow: the contract's loop over ONE channel.  modem6 = {mark_step, space_step, baud_step, window, loop_shift, nrzi};
+ *         pcm [n_blocks][512], n_pcm [n_blocks] or NULL; state18: the channel's 18 dwords (16 of sample pairs, phi, then
+ *         h[n-1] in bit 0 and last in bit 1), zero for a fresh channel, read and replaced; bits (at least
+ *         hrfd_afsk_max_bits bytes) with n_bits (one count), and hard [n_blocks][64], as hrfd_afsk_process takes them.
+ * tests/test_afsk_model.py holds tests/afsk_model.py against both. */
+int hrfd_afsk_debug_taps(uint32_t mark_step, uint32_t space_step, uint32_t window, int16_t *out128);
+int hrfd_afsk_debug_slow(const uint32_t *modem6, uint64_t min_power, const int16_t *pcm, const uint32_t *n_pcm, uint32_t n_blocks,
+                         uint32_t *state18, uint8_t *bits, uint32_t *n_bits, uint8_t *hard);
+
 /* ------------------------------------------------------------------ behaviour-changing hooks (HRFD_DEBUG_HOOKS=1) */
 int hrfd_rx_debug_set_atan(hrfd_rx *h, int mode);        /* -1 automatic, 0 table gather, 1 arithmetic */
 int hrfd_rx_debug_set_warm(hrfd_rx *h, int warm);        /* shrink the de-emphasis warm-up, seeds off: forces repairs */
