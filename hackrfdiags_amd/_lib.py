@@ -281,6 +281,21 @@ def load() -> C.CDLL:
         L.hrfd_afsk_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]
         L.hrfd_afsk_debug_taps.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, _i16p]
         L.hrfd_afsk_debug_slow.argtypes = [_u32p, C.c_uint64, _vp, _vp, C.c_uint32, _u32p, _vp, _vp, _vp]
+    if hasattr(L, "hrfd_afskgen_create"):                  # (an older build named by HRFD_LIB has no AFSK generator bank)
+        L.hrfd_afskgen_create.argtypes = [C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_afskgen_destroy.argtypes = [_vp]
+        L.hrfd_afskgen_queue.argtypes = [_vp, C.c_uint32, _vp, _vp, C.c_uint64]
+        L.hrfd_afskgen_cut.argtypes = [_vp, C.c_uint32]
+        L.hrfd_afskgen_reset.argtypes = [_vp]
+        L.hrfd_afskgen_set_time.argtypes = [_vp, C.c_uint64]
+        L.hrfd_afskgen_time.argtypes = [_vp, _u64p]
+        L.hrfd_afskgen_pending.argtypes = [_vp, C.c_uint32, _u32p, _u64p]
+        L.hrfd_afskgen_get_clips.argtypes = [_vp, C.c_uint32, _u64p]
+        L.hrfd_afskgen_process.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp]
+        L.hrfd_afskgen_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp]
+        L.hrfd_afskgen_debug_levels.argtypes = [_vp, C.c_uint32, C.c_int, _vp]
+        L.hrfd_afskgen_debug_length.argtypes = [C.c_uint32, C.c_uint32, _u64p]
+        L.hrfd_afskgen_debug_slow.argtypes = [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _u64p]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

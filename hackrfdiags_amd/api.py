@@ -1567,6 +1567,132 @@ class Afsk(_Bank):
                    _ptr(d_n_bits), _ptr(d_hard), _ptr(stream))
 
 
+AFSKGEN_MAX_MESSAGES = 4
+AFSKGEN_MAX_BITS = 8192
+AFSKGEN_MAX_BLOCKS = 1024
+AFSKGEN_NRZI = 1
+AFSKGEN_APPEND = 0xFFFFFFFFFFFFFFFF
+AFSKGEN_RAMP = 64
+
+
+def hdlc_encode(payloads, n_lead_flags: int = 12, n_between: int = 2, n_tail_flags: int = 3) -> np.ndarray:
+    """the bit stream of HDLC frames for AfskGen.queue, one uint8 of 0 / 1 per bit, host only: n_lead_flags 0x7E flags, then
+    per frame the payload and its CRC-16/X.25, low byte first, every byte LSB first, a zero stuffed behind five ones, with
+    n_between flags between frames and n_tail_flags behind the last.  The inverse of hdlc_frames.  The first and the last 64
+    samples of a message are ramped, about ten bits at 1200 baud: that is what the lead and tail flags are for, so keep at
+    least a dozen in front and two behind."""
+    flag = [0, 1, 1, 1, 1, 1, 1, 0]
+    payloads = [bytes(p) for p in payloads]
+    out = flag * int(n_lead_flags)
+    for i, p in enumerate(payloads):
+        crc = crc16_x25(p)
+        ones = 0
+        for byte in p + bytes([crc & 255, crc >> 8]):
+            for k in range(8):
+                b = (byte >> k) & 1
+                out.append(b)
+                ones = ones + 1 if b else 0
+                if ones == 5:
+                    out.append(0)
+                    ones = 0
+        out += flag * int(n_between if i + 1 < len(payloads) else n_tail_flags)
+    return np.array(out, dtype=np.uint8)
+
+
+class AfskGen(_Bank):
+    """The AFSK generator bank (hrfd_afskgen_*): packet data on the PCM of n_channels transmit channels, the mirror of Afsk.
+    Messages of up to 8192 bits, each with a modem of its own (Bell 202 by default), are queued per channel at absolute
+    stream times, at most four that have not ended, and added, saturating, to the rows Mod and Duc.transmit read, as
+    continuous-phase AFSK with a ramp of 8 ms at either end.  Exact in integers on the tone generator's phase grid, and
+    independent of how a stream is cut into calls; it composes with ToneGen by running one behind the other, in place.
+    (Its kernel is one launch of one workgroup per channel, so like Leveler and Afsk it has no chunked launch and no
+    debug_set_max_wgs.)"""
+
+    _prefix = "afskgen"
+
+    def __init__(self, n_channels: int, device: int = 0):
+        self.n = int(n_channels)
+        self._create(self.n, device)
+
+    def queue(self, channel: int, bits, mark_hz: float = 1200, space_hz: float = 2200, baud: float = 1200, amplitude: int = 8000,
+              nrzi: bool = True, start: int = AFSKGEN_APPEND, gap: int = 0, steps=None):
+        """one message of 1..8192 bits (one value per bit, only bit 0 counts: a row of Afsk's bits can be queued as it is) on
+        one channel or on all (ALL); it begins at start + gap, start AFSKGEN_APPEND = max(time, the end of the channel's last
+        message).  steps = (mark_step, space_step, baud_step) overrides the three rates.  Refused whole if anything is out
+        of order."""
+        b = np.ascontiguousarray(np.asarray(bits).ravel() & 1, dtype=np.uint8)
+        m, s, r = (int(v) for v in steps) if steps is not None else (afsk_step(mark_hz), afsk_step(space_hz), afsk_step(baud))
+        msg = [int(gap), int(b.size), m, s, r, int(amplitude), AFSKGEN_NRZI if nrzi else 0, 0]
+        if any(v < 0 or v > 0xFFFFFFFF for v in msg):
+            raise ValueError(f"gap, the bit count, the steps and the amplitude must fit uint32, got {msg[:6]}")
+        if not 0 <= int(start) <= AFSKGEN_APPEND:
+            raise ValueError(f"start {start}")
+        a = np.array(msg, dtype=np.uint32)
+        self._call("queue", int(channel), _ptr(a), _ptr(b), int(start))
+
+    def send(self, channel: int, payloads, **modem):
+        """queue(channel, hdlc_encode(payloads), ...): one message of HDLC frames with the default flag counts"""
+        self.queue(channel, hdlc_encode(payloads), **modem)
+
+    def cut(self, channel: int = ALL):
+        """ramp the message in progress down over the next 64 samples and drop those not yet begun"""
+        self._call("cut", int(channel))
+
+    def reset(self):
+        """empty every queue, time = 0, clips = 0"""
+        self._call("reset")
+
+    def set_time(self, N: int):
+        """move the clock; refused while a channel holds a message that has not ended"""
+        self._call("set_time", int(N))
+
+    def time(self) -> int:
+        """the stream time of the next call's first sample"""
+        v = C.c_uint64(0)
+        self._call("time", C.byref(v))
+        return int(v.value)
+
+    def pending(self, channel: int):
+        """(messages of the channel that have not ended, the end of the last of them: the time itself where there is none)"""
+        n, end = C.c_uint32(0), C.c_uint64(0)
+        self._call("pending", int(channel), C.byref(n), C.byref(end))
+        return int(n.value), int(end.value)
+
+    def clips(self, channel: int) -> int:
+        """samples of the channel the saturation changed, since create or reset; blocking"""
+        v = C.c_uint64(0)
+        self._call("get_clips", int(channel), C.byref(v))
+        return int(v.value)
+
+    def process(self, pcm, n_blocks: int = None, want_active: bool = False):
+        """pcm int16 [n_channels, n_blocks, 512], or None with n_blocks (generate only) -> out int16 [n_channels, n_blocks,
+        512], or (out, active uint8 [n_channels, n_blocks]) with want_active; blocking"""
+        x = None
+        if pcm is not None:
+            x = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.n, -1)
+            if x.shape[1] % 512 != 0 or (n_blocks is not None and x.shape[1] != 512 * int(n_blocks)):
+                raise ValueError(f"a channel's PCM must be whole blocks of 512 samples, got {x.shape[1]} samples")
+            n_blocks = x.shape[1] // 512
+        elif n_blocks is None:
+            raise ValueError("generate only needs n_blocks")
+        n_blocks = int(n_blocks)
+        if n_blocks < 0 or n_blocks > 0xFFFFFFFF:
+            raise ValueError(f"n_blocks {n_blocks}")
+        out = np.zeros((self.n, min(n_blocks, AFSKGEN_MAX_BLOCKS), 512), dtype=np.int16)
+        active = np.zeros((self.n, min(n_blocks, AFSKGEN_MAX_BLOCKS)), dtype=np.uint8) if want_active else None
+        self._call("process", _ptr(x), n_blocks, _ptr(out), _ptr(active))
+        return (out, active) if want_active else out
+
+    def process_device(self, d_pcm, channel_stride: int, n_blocks: int, d_out, out_stride: int = 0, d_active=None, stream=None):
+        """device pointers (ints); d_pcm None = generate only, d_active may be None; out_stride 0 = the input's stride where
+        d_out is d_pcm (in place), dense rows otherwise; asynchronous on stream (None = the handle's own)"""
+        if not out_stride:
+            in_place = d_pcm is not None and d_out is not None and _ptr(d_out).value == _ptr(d_pcm).value
+            out_stride = int(channel_stride) if in_place else 1024 * int(n_blocks)
+        self._call("process_device", _ptr(d_pcm), int(channel_stride), int(n_blocks), _ptr(d_out), int(out_stride), _ptr(d_active),
+                   _ptr(stream))
+
+
 class Engine:
     """Factory with the interface tests/goldencheck.py expects."""
 

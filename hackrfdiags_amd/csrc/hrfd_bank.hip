@@ -1,5 +1,5 @@
 // hackrfdiags_amd/csrc/hrfd_bank.hip -- the host core of the bank handles (hrfd_ddc, hrfd_duc, hrfd_spec, hrfd_cal,
-// hrfd_tone, hrfd_audio, hrfd_resamp, hrfd_level, hrfd_tonegen, hrfd_afsk) and of the transmit handles (hrfd_mod, hrfd_nco): device and stream ownership with the three ordering rules (BankCore), what stands
+// hrfd_tone, hrfd_audio, hrfd_resamp, hrfd_level, hrfd_tonegen, hrfd_afsk, hrfd_afskgen) and of the transmit handles (hrfd_mod, hrfd_nco): device and stream ownership with the three ordering rules (BankCore), what stands
 // around every launch (the NULL-handle refusal, the launch check, the chunked launch, the loop over the selected channels),
 // the blocking host entry (BankHostCall), the history of the PCM banks (BankHistory), and the setters and argument checks
 // the DDC and the DUC share.  DESIGN.md 3.5a states the rules; hrfd_bank.h and hrfd_pcm.h hold the parts that need no HIP,

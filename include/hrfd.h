@@ -1015,6 +1015,98 @@ int hrfd_afsk_process_device(hrfd_afsk *a, const int16_t *d_pcm, uint64_t channe
                              void *stream);
 
 /* ------------------------------------------------------------------------------
+ * AFSK generator bank: packet data keyed onto the PCM of C transmit channels: continuous-phase audio frequency-shift keying,
+ * added to the rows that hrfd_mod_* and hrfd_duc_transmit read.  The mirror of the AFSK bank, which decodes what it sends,
+ * on the tone generator's phase grid; the two generators compose by running one after the other, in place, on the same
+ * rows.  PCM rows [C][n_blocks][512] int16 at 8 kS/s; there is no n_pcm, and every sample of every block is written.  Exact
+ * integer arithmetic, the same on every device (tests/afskgen_model.py restates it); shifts are arithmetic.  Everything is
+ * per channel, the modem included: it travels in the message.
+ *   sizes     C = 1..65536 channels, fixed at create; n_blocks = 1..HRFD_AFSKGEN_MAX_BLOCKS = 1024; at most
+ *             HRFD_AFSKGEN_MAX_MESSAGES = 4 messages per channel that have not ended.  The device's copy of the queues is
+ *             4 KiB of levels and 128 bytes of descriptors a channel: 264 MiB at 65536 channels.
+ *   time      the handle keeps one uint64 sample counter N, the stream time of the next call's first sample.  Every call
+ *             advances it by 512 n_blocks, on the host.  Every stream time stays below 2^63.
+ *   message   {gap, n_bits, mark_step, space_step, baud_step, amp, flags, pad}, eight uint32, with B = n_bits =
+ *             1..HRFD_AFSKGEN_MAX_BITS = 8192 data bits d[i], one byte per bit of which only bit 0 counts (the format
+ *             hrfd_afsk_process writes), and a start S (uint64 stream time).  The three steps = round(f / 8000 * 2^32),
+ *             1..2^31; amp = 0..32767; flags: bit 0 = HRFD_AFSKGEN_NRZI, the others 0; pad = 0.
+ *   levels    without NRZI l[i] = d[i] & 1.  With NRZI l[-1] = 1 (mark), l[i] = l[i-1] where d[i] & 1, else 1 - l[i-1]:
+ *             the inverse of the AFSK bank's 1 - (h ^ last).
+ *   length    L = ceil(B 2^32 / baud_step), the least k with (k baud_step) >> 32 >= B.  L >= 2^31 is refused.  E = S + L;
+ *             E >= 2^63 is refused.
+ *   law       at stream time n, k = n - S, 0 <= k < L:
+ *               bit(k) = (k baud_step) >> 32              (a 64-bit product; < B by the definition of L)
+ *               st(k) = l[bit(k)] ? mark_step : space_step
+ *               theta(0) = 0, theta(k + 1) = (theta(k) + st(k)) mod 2^32       (the phase is continuous across the bits)
+ *               i = ((theta(k) + 2^19) >> 20) & 4095
+ *               s = COS[(i - 1024) & 4095]                (the tone generator's sine index: k = 0 is a zero crossing)
+ *               v = (amp s + 2^14) >> 15
+ *               e = min(k + 1, E - n, 64)
+ *               g = (v e + 32) >> 6
+ *             the tone generator's mix with one tone and its ramp of 64 samples (8 ms) at both ends.  With mark_step ==
+ *             space_step a message is sample for sample the tone generator's segment of that start, length, step and amp.
+ *   output    messages of one channel never overlap, so a sample has at most one g.  y = sat16(x + g); x is the input
+ *             sample, or 0 when the call has no input (generate only).  clips[c] counts the samples where the saturation
+ *             changed the value, until hrfd_afskgen_reset.
+ *   active    optional uint8 [C][n_blocks]: 1 where a message has a sample in the block, else 0: the transmitter's key.
+ * The output at stream time n is a pure function of n, the message and x: however a stream is cut into calls, it comes out
+ * the same.  Messages that have ended (E <= N) leave the queue with the next call, hrfd_afskgen_queue or hrfd_afskgen_cut.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well).  No setter waits for the device:
+ * what changed is copied to the device on the next call's stream, ahead of its launch, and a call that already runs keeps the
+ * queue it was launched with.  Calls may use different streams: each launch is ordered on the device behind the handle's
+ * previous one.
+ *   hrfd_afskgen_queue          one message of bits[0..n_bits) on one channel, or on all (HRFD_ALL_CHANNELS).  It begins at
+ *                               start + gap; start = HRFD_AFSKGEN_APPEND: max(N, the end of the channel's last message),
+ *                               per channel.  Refused whole (HRFD_EINVAL, nothing queued on any channel): a start before
+ *                               N, an overlap, a fifth message that has not ended, n_bits outside 1..8192, a step outside
+ *                               1..2^31, an amp above 32767, other flags, a pad, L >= 2^31, a time at or above 2^63
+ *   hrfd_afskgen_cut            one channel, or all: the message in progress at N (S <= N < E) is trimmed to end at
+ *                               min(E, N + 64), which under the law is a ramp down; those not yet begun are dropped
+ *   hrfd_afskgen_reset          empties every queue, N = 0, clips = 0
+ *   hrfd_afskgen_set_time       moves the clock; refused while any channel holds a message that has not ended (a clock that
+ *                               jumps into a message would need the sum of its steps up to there)
+ *   hrfd_afskgen_time           N
+ *   hrfd_afskgen_pending        of one channel: the messages that have not ended at N, and the end of the last of them (N
+ *                               where there is none); either result may be NULL, not both
+ *   hrfd_afskgen_get_clips      clips[channel]; blocks until the handle's calls have run
+ *   hrfd_afskgen_process        host buffers, dense: pcm [C][n_blocks][512] or NULL (generate only) -> out [C][n_blocks][512],
+ *                               active [C][n_blocks] or NULL.  out may be pcm itself; blocking
+ *   hrfd_afskgen_process_device device buffers; input rows channel_stride_bytes apart, rows of d_out out_stride_bytes apart
+ *                               (both even and >= 1024 n_blocks), d_pcm and d_out at any even address, d_active dense.  d_pcm
+ *                               may be NULL (generate only; its stride is not looked at).  In place is allowed: d_out at exactly
+ *                               the input's address with the same stride; a row no message touches in the call is then
+ *                               neither read nor written.  Any other overlap of d_out and the input is refused.
+ *                               Asynchronous on `stream` (a hipStream_t, NULL = the handle's own)
+ */
+typedef struct hrfd_afskgen hrfd_afskgen;
+typedef struct hrfd_afskgen_message
+{
+  uint32_t gap;                            /* samples of silence in front of the message */
+  uint32_t n_bits;                         /* data bits, 1..HRFD_AFSKGEN_MAX_BITS */
+  uint32_t mark_step, space_step, baud_step;
+  uint32_t amp;
+  uint32_t flags;                          /* HRFD_AFSKGEN_NRZI or 0 */
+  uint32_t pad;                            /* 0 */
+} hrfd_afskgen_message;
+#define HRFD_AFSKGEN_MAX_MESSAGES 4
+#define HRFD_AFSKGEN_MAX_BITS 8192
+#define HRFD_AFSKGEN_MAX_BLOCKS 1024
+#define HRFD_AFSKGEN_NRZI 1u
+#define HRFD_AFSKGEN_APPEND UINT64_MAX
+int hrfd_afskgen_create(uint32_t n_channels, int device, hrfd_afskgen **out);
+int hrfd_afskgen_destroy(hrfd_afskgen *g);
+int hrfd_afskgen_queue(hrfd_afskgen *g, uint32_t channel, const hrfd_afskgen_message *msg, const uint8_t *bits, uint64_t start);
+int hrfd_afskgen_cut(hrfd_afskgen *g, uint32_t channel);
+int hrfd_afskgen_reset(hrfd_afskgen *g);
+int hrfd_afskgen_set_time(hrfd_afskgen *g, uint64_t N);
+int hrfd_afskgen_time(hrfd_afskgen *g, uint64_t *N);
+int hrfd_afskgen_pending(hrfd_afskgen *g, uint32_t channel, uint32_t *n_messages, uint64_t *end);
+int hrfd_afskgen_get_clips(hrfd_afskgen *g, uint32_t channel, uint64_t *n);
+int hrfd_afskgen_process(hrfd_afskgen *g, const int16_t *pcm, uint32_t n_blocks, int16_t *out, uint8_t *active);
+int hrfd_afskgen_process_device(hrfd_afskgen *g, const int16_t *d_pcm, uint64_t channel_stride_bytes, uint32_t n_blocks,
+                                int16_t *d_out, uint64_t out_stride_bytes, uint8_t *d_active, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",

@@ -74,6 +74,21 @@ int hrfd_afsk_debug_taps(uint32_t mark_step, uint32_t space_step, uint32_t windo
 int hrfd_afsk_debug_slow(const uint32_t *modem6, uint64_t min_power, const int16_t *pcm, const uint32_t *n_pcm, uint32_t n_blocks,
                          uint32_t *state18, uint8_t *bits, uint32_t *n_bits, uint8_t *hard);
 
+/* the AFSK generator bank's laws as the host states them (hrfd_afskgen.h), no device needed; host pointers.
+ *   levels: bits [n_bits] (1..8192, bit 0 of every byte) -> words [(n_bits + 31) / 32]: bit i & 31 of word i >> 5 = l[i].
+ *   length: L of n_bits (any above 0: the law, not the queue's limit) at baud_step, or the refusal of L >= 2^31.
+ *   slow:   the contract's loop over ONE channel and one call.  msgs [n_msgs] (at most 4) with their bits one behind the
+ *           other in `bits`; message j begins at starts[j] + msgs[j].gap and ends at its E, or at ends[j] where ends is
+ *           given and ends[j] lies in front of E (a cut message).  N: the stream time of the call's first sample; pcm
+ *           [n_blocks][512] or NULL; out [n_blocks][512] (may be pcm), active [n_blocks] or NULL, *clips (may be NULL) as
+ *           hrfd_afskgen_process gives them.  Overlapping messages are refused.
+ * tests/test_afskgen_model.py holds tests/afskgen_model.py against all three. */
+int hrfd_afskgen_debug_levels(const uint8_t *bits, uint32_t n_bits, int nrzi, uint32_t *words);
+int hrfd_afskgen_debug_length(uint32_t n_bits, uint32_t baud_step, uint64_t *length);
+int hrfd_afskgen_debug_slow(const hrfd_afskgen_message *msgs, const uint8_t *bits, const uint64_t *starts, const uint64_t *ends,
+                            uint32_t n_msgs, uint64_t N, const int16_t *pcm, uint32_t n_blocks, int16_t *out, uint8_t *active,
+                            uint64_t *clips);
+
 /* ------------------------------------------------------------------ behaviour-changing hooks (HRFD_DEBUG_HOOKS=1) */
 int hrfd_rx_debug_set_atan(hrfd_rx *h, int mode);        /* -1 automatic, 0 table gather, 1 arithmetic */
 int hrfd_rx_debug_set_warm(hrfd_rx *h, int warm);        /* shrink the de-emphasis warm-up, seeds off: forces repairs */
