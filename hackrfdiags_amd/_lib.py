@@ -296,6 +296,17 @@ def load() -> C.CDLL:
         L.hrfd_afskgen_debug_levels.argtypes = [_vp, C.c_uint32, C.c_int, _vp]
         L.hrfd_afskgen_debug_length.argtypes = [C.c_uint32, C.c_uint32, _u64p]
         L.hrfd_afskgen_debug_slow.argtypes = [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _u64p]
+    if hasattr(L, "hrfd_hdlc_create"):                     # (an older build named by HRFD_LIB has no HDLC bank)
+        L.hrfd_hdlc_create.argtypes = [C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_hdlc_destroy.argtypes = [_vp]
+        L.hrfd_hdlc_set_limits.argtypes = [_vp, C.c_uint32, C.c_uint32]
+        L.hrfd_hdlc_set_require_carrier.argtypes = [_vp, C.c_int]
+        L.hrfd_hdlc_reset.argtypes = [_vp, C.c_uint32]
+        L.hrfd_hdlc_max_out.argtypes = [_vp, C.c_uint32, _u32p]
+        L.hrfd_hdlc_process.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]
+        L.hrfd_hdlc_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]
+        L.hrfd_hdlc_debug_slow.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp]
+        L.hrfd_hdlc_debug_max_out.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, _u32p]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

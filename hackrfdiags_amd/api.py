@@ -1567,6 +1567,94 @@ class Afsk(_Bank):
                    _ptr(d_n_bits), _ptr(d_hard), _ptr(stream))
 
 
+HDLC_MAX_BITS = 1 << 20
+HDLC_MAX_PAYLOAD = 1021
+
+
+def hdlc_max_out(max_bits: int, min_payload: int = 1, max_payload: int = 512) -> int:
+    """a row of records that never drops: 11 F + min(F P, P + max_bits / 8) rounded up to 4, F = 1 + (max_bits - 1) / (8 (m + 3))"""
+    F = 1 + (int(max_bits) - 1) // (8 * (int(min_payload) + 3))
+    P = int(max_payload)
+    return (11 * F + min(F * P, P + int(max_bits) // 8) + 3) & ~3
+
+
+class Hdlc(_Bank):
+    """The HDLC bank (hrfd_hdlc_*): the rows of bits Afsk.process_device writes in, read where they lie on the device, the
+    packet frames in them out: per channel a row of records (end_bit, n_payload, fcs, payload) of the frames whose
+    CRC-16/X.25 is good, and the counts of records, bad frames and dropped records.  The state (a partial frame, the run of
+    ones) lives on the device: a stream may be cut into calls anywhere.  With require_carrier off the payloads are those of
+    hdlc_frames over the joined stream that have at most max_payload bytes.  (One launch of one workgroup per channel, so
+    like Afsk it has no chunked launch and no debug_set_max_wgs.)"""
+
+    _prefix = "hdlc"
+
+    def __init__(self, n_channels: int, min_payload: int = 1, max_payload: int = 512, require_carrier: bool = False, device: int = 0):
+        self.n = int(n_channels)
+        self._create(self.n, device)
+        if (int(min_payload), int(max_payload)) != (1, 512):
+            self.set_limits(min_payload, max_payload)
+        if require_carrier:
+            self.set_require_carrier(True)
+
+    def set_limits(self, min_payload: int = 1, max_payload: int = 512):
+        """payloads of min_payload..max_payload bytes (1..1021); resets every channel"""
+        for name, v in (("min_payload", min_payload), ("max_payload", max_payload)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} must fit uint32, got {v}")
+        self._call("set_limits", int(min_payload), int(max_payload))
+
+    def set_require_carrier(self, on: bool):
+        """on: a bit without the carrier flag ends the frame it lies in"""
+        self._call("set_require_carrier", 1 if on else 0)
+
+    def reset(self, channel: int = ALL):
+        """forget the partial frame of one channel, or of all"""
+        self._call("reset", int(channel))
+
+    def max_out(self, max_bits: int) -> int:
+        """the bytes of a row of records that never drops for a call of max_bits bits under the handle's limits"""
+        v = C.c_uint32(0)
+        self._call("max_out", int(max_bits), C.byref(v))
+        return int(v.value)
+
+    @staticmethod
+    def parse(row, n_frames: int):
+        """the first n_frames records of a row of records (uint8) -> [(end_bit, payload bytes, fcs)]"""
+        row = np.ascontiguousarray(row, dtype=np.uint8).ravel()
+        frames, at = [], 0
+        for _ in range(int(n_frames)):
+            end_bit, n, fcs = (int(v) for v in np.frombuffer(row[at:at + 8].tobytes(), dtype="<u4,<u2,<u2")[0])
+            frames.append((end_bit, row[at + 8:at + 8 + n].tobytes(), fcs))
+            at += 8 + ((n + 3) & ~3)
+        return frames
+
+    def process(self, bits_list, out_bytes: int = None, want_counts: bool = False):
+        """bits_list: per channel a uint8 array of bits as Afsk.process gives them (any lengths) -> per channel
+        [(end_bit, payload)] of the good frames that close in this call; with want_counts also (n_frames, n_bad, dropped),
+        uint32 [n_channels] each.  out_bytes: the row of records, max_out of the longest row unless given; blocking"""
+        if len(bits_list) != self.n:
+            raise ValueError(f"need the bits of {self.n} channels, got {len(bits_list)}")
+        rows = [np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in bits_list]
+        max_bits = max(1, max(len(r) for r in rows))
+        dense = np.zeros((self.n, max_bits), dtype=np.uint8)
+        for c, r in enumerate(rows):
+            dense[c, :len(r)] = r
+        n_bits = np.array([len(r) for r in rows], dtype=np.uint32)
+        out_bytes = self.max_out(max_bits) if out_bytes is None else int(out_bytes)
+        out = np.zeros((self.n, out_bytes), dtype=np.uint8)
+        n_frames, n_bad, dropped = (np.zeros(self.n, dtype=np.uint32) for _ in range(3))
+        self._call("process", _ptr(dense), _ptr(n_bits), max_bits, _ptr(out), out_bytes, _ptr(n_frames), _ptr(n_bad), _ptr(dropped))
+        frames = [[(e, p) for e, p, _ in self.parse(out[c], n_frames[c])] for c in range(self.n)]
+        return (frames, (n_frames, n_bad, dropped)) if want_counts else frames
+
+    def process_device(self, d_bits, bits_stride: int, d_n_bits, max_bits: int, d_out, out_stride: int, out_bytes: int, d_n_frames,
+                       d_n_bad, d_dropped, stream=None):
+        """device pointers (ints): the rows of bits and counts of Afsk.process_device, max_bits the most a row holds; rows of
+        records out_stride apart of out_bytes each; d_n_bad may be None; asynchronous on stream (None = the handle's own)"""
+        self._call("process_device", _ptr(d_bits), int(bits_stride), _ptr(d_n_bits), int(max_bits), _ptr(d_out), int(out_stride),
+                   int(out_bytes), _ptr(d_n_frames), _ptr(d_n_bad), _ptr(d_dropped), _ptr(stream))
+
+
 AFSKGEN_MAX_MESSAGES = 4
 AFSKGEN_MAX_BITS = 8192
 AFSKGEN_MAX_BLOCKS = 1024

@@ -1,5 +1,5 @@
 // hackrfdiags_amd/csrc/hrfd_bank.hip -- the host core of the bank handles (hrfd_ddc, hrfd_duc, hrfd_spec, hrfd_cal,
-// hrfd_tone, hrfd_audio, hrfd_resamp, hrfd_level, hrfd_tonegen, hrfd_afsk, hrfd_afskgen) and of the transmit handles (hrfd_mod, hrfd_nco): device and stream ownership with the three ordering rules (BankCore), what stands
+// hrfd_tone, hrfd_audio, hrfd_resamp, hrfd_level, hrfd_tonegen, hrfd_afsk, hrfd_afskgen, hrfd_hdlc) and of the transmit handles (hrfd_mod, hrfd_nco): device and stream ownership with the three ordering rules (BankCore), what stands
 // around every launch (the NULL-handle refusal, the launch check, the chunked launch, the loop over the selected channels),
 // the blocking host entry (BankHostCall), the history of the PCM banks (BankHistory), and the setters and argument checks
 // the DDC and the DUC share.  DESIGN.md 3.5a states the rules; hrfd_bank.h and hrfd_pcm.h hold the parts that need no HIP,
@@ -234,7 +234,8 @@ private:
 // The filter history of a PCM bank (hrfd_audio, hrfd_resamp): per channel the last 512 samples as the filter saw them, as
 // 256 packed pairs, in a ping-pong of two sides (a launch reads in() and writes out(), flip() turns them over), and the
 // channels that start from zeros with the next launch.  hrfd_level keeps its 64 frame peaks per channel the same way, in
-// rows of 32 dwords, hrfd_afsk its samples, phase and flags in rows of 18.  Host fields under the handle's core.mu.
+// rows of 32 dwords, hrfd_afsk its samples, phase and flags in rows of 18, hrfd_hdlc its
+// partial frame in rows of 260.  Host fields under the handle's core.mu.
 struct BankHistory
 {
   static constexpr size_t kDw = 256;       // dwords per channel, unless alloc is told otherwise

@@ -1,5 +1,5 @@
 // hackrfdiags_amd/csrc/hrfd_pcm.h -- the PCM contract of the banks behind the receive chain (hrfd_tone, hrfd_audio,
-// hrfd_resamp, hrfd_level, hrfd_afsk) and in front of the transmit chain (hrfd_tonegen, hrfd_afskgen), in one place: rows of int16 at an even address, an even stride apart, in blocks of 512 samples of
+// hrfd_resamp, hrfd_level, hrfd_afsk, and hrfd_hdlc behind that) and in front of the transmit chain (hrfd_tonegen, hrfd_afskgen), in one place: rows of int16 at an even address, an even stride apart, in blocks of 512 samples of
 // which an optional n_pcm says how many count; the rounding of a FIR over them; and the argument checks the banks share.
 // Plain C++ like hrfd_bank.h (tests/cpp/san_pcm.cc compiles it on the CPU); the includer declares
 // `int fail(int code, const char *fmt, ...)` and the HRFD_* codes first.

@@ -1107,6 +1107,79 @@ int hrfd_afskgen_process_device(hrfd_afskgen *g, const int16_t *d_pcm, uint64_t 
                                 int16_t *d_out, uint64_t out_stride_bytes, uint8_t *d_active, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * HDLC bank: the bits of C channels -> the packet frames in them (HDLC as AX.25 / APRS uses it): flags, bit stuffing, aborts
+ * and the CRC-16/X.25 frame check, on the device.  It reads what hrfd_afsk_process_device writes, where it lies: rows of
+ * bits, one byte a bit, bits_stride_bytes apart, and the counts d_n_bits [C], which the kernel reads on the device: no call
+ * waits for it.  The law is per channel and bit by bit, the same on every device and however a stream is cut into calls
+ * (tests/hdlc_model.py restates it):
+ *   sizes     C = 1..65536 channels, fixed at create.  Per call max_bits = 1..HRFD_HDLC_MAX_BITS = 2^20; channel c uses
+ *             min(d_n_bits[c], max_bits) bits.  bits_stride_bytes >= max_bits, rows at any address.  A longest payload of
+ *             P = 1..HRFD_HDLC_MAX_PAYLOAD = 1021 bytes and a shortest of m = 1..P; a flag require_carrier.
+ *   bit       a byte of the row: v = byte & HRFD_AFSK_BIT, c = (byte >> 1) & 1 (HRFD_AFSK_CARRIER).
+ *   state     ones (0..7, saturating), in_frame, and the n bits collected so far, packed LSB first, at most
+ *             cap = 8 (P + 2) + 7.  A channel starts with ones = 0, no frame open, n = 0.
+ *   law       for every bit, in this order:
+ *               0. if require_carrier and c == 0: in_frame = false.  The bit is then processed as usual
+ *               1. v == 1: ones = min(7, ones + 1); if in_frame, append 1; if ones == 7, in_frame = false (an abort)
+ *               2. v == 0 and ones == 6, a flag: if in_frame and n >= 7 + 8 (m + 2) and (n - 7) % 8 == 0, the first n - 7
+ *                  bits are whole bytes, LSB first, the last two of them the check sequence, low byte first.  The frame is
+ *                  good if the sequence is the CRC-16/X.25 of the bytes before it (equivalently: the CRC register, from
+ *                  0xFFFF over all the bytes, ends at 0xF0B8), else it is bad.  Then in_frame = true, n = 0
+ *               3. v == 0 and ones == 5: a stuffed zero, dropped
+ *               4. v == 0 otherwise: if in_frame, append 0
+ *               5. after any zero, ones = 0
+ *             Appending when n == cap sets in_frame = false instead: an over-long frame is dead until the next flag.
+ *             With require_carrier off the good frames are those of a plain flag / stuffing / CRC walk over the joined
+ *             stream (api.hdlc_frames) that have at most P bytes.
+ *   record    uint32 end_bit (the index in this call's row of the closing flag's last bit), uint16 n_payload, uint16 fcs
+ *             (the check sequence as sent), the payload, zeros up to a multiple of 4: 8 + ((n_payload + 3) & ~3) bytes.
+ *   outputs   a row of out_bytes bytes (a multiple of 4) per channel, rows out_stride_bytes apart: the good frames in stream
+ *             order, one record behind the other.  A record that does not fit the row is dropped, and so is every good
+ *             frame of the call behind it: d_n_frames [C] counts the records written, d_dropped [C] the good frames that were
+ *             not (never partly written), d_n_bad [C] (optional) the bad frames of the call: a link-quality meter.  Bytes
+ *             of a row behind its last record are not written.
+ *   bound     a row of hrfd_hdlc_max_out(max_bits) bytes never drops: the closing bits of two frames of valid length lie at
+ *             least 8 (m + 3) bits apart, so a call closes at most F = 1 + (max_bits - 1) / (8 (m + 3)); their payloads sum
+ *             to at most min(F P, P + max_bits / 8) bytes (the carried partial frame and the call's bits); a record is at
+ *             most 11 bytes more than its payload: 11 F + min(F P, P + max_bits / 8), rounded up to 4.
+ *   state     per channel ones, in_frame, n and the partial frame: 260 dwords, on the device (twice: 2080 bytes a channel).
+ *   defaults  m = 1, P = 512, require_carrier off.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well).  Setters never wait for the
+ * device.  Calls may use different streams: each launch is ordered on the device behind the handle's previous one, so a call
+ * chains behind the hrfd_afsk_process_device call that filled its input when both are given the same stream.
+ *   hrfd_hdlc_set_limits          m and P; resets every channel: a partial frame under another bound means nothing
+ *   hrfd_hdlc_set_require_carrier for every channel; keeps the state
+ *   hrfd_hdlc_reset               the state of one channel, or of all (HRFD_ALL_CHANNELS), from the next call on
+ *   hrfd_hdlc_max_out             the bound above for max_bits under the handle's limits
+ *   hrfd_hdlc_process             host buffers, dense: bits [C][max_bits], n_bits [C] -> out [C][out_bytes], n_frames [C],
+ *                                 n_bad [C] or NULL, dropped [C]; blocking
+ *   hrfd_hdlc_process_device      device buffers; d_out 4-byte aligned, out_stride_bytes a multiple of 4 and >= out_bytes;
+ *                                 the counts dense and 4-byte aligned.  Asynchronous on `stream` (a hipStream_t, NULL = the
+ *                                 handle's own)
+ */
+typedef struct hrfd_hdlc hrfd_hdlc;
+#define HRFD_HDLC_MAX_BITS (1u << 20)
+#define HRFD_HDLC_MAX_PAYLOAD 1021
+typedef struct hrfd_hdlc_record
+{
+  uint32_t end_bit;
+  uint16_t n_payload;
+  uint16_t fcs;
+  /* the payload, zero-padded to a multiple of 4 */
+} hrfd_hdlc_record;
+int hrfd_hdlc_create(uint32_t n_channels, int device, hrfd_hdlc **out);
+int hrfd_hdlc_destroy(hrfd_hdlc *h);
+int hrfd_hdlc_set_limits(hrfd_hdlc *h, uint32_t min_payload, uint32_t max_payload);
+int hrfd_hdlc_set_require_carrier(hrfd_hdlc *h, int on);
+int hrfd_hdlc_reset(hrfd_hdlc *h, uint32_t channel);
+int hrfd_hdlc_max_out(hrfd_hdlc *h, uint32_t max_bits, uint32_t *out_bytes);
+int hrfd_hdlc_process(hrfd_hdlc *h, const uint8_t *bits, const uint32_t *n_bits, uint32_t max_bits, uint8_t *out, uint32_t out_bytes,
+                      uint32_t *n_frames, uint32_t *n_bad, uint32_t *dropped);
+int hrfd_hdlc_process_device(hrfd_hdlc *h, const uint8_t *d_bits, uint64_t bits_stride_bytes, const uint32_t *d_n_bits,
+                             uint32_t max_bits, uint8_t *d_out, uint64_t out_stride_bytes, uint32_t out_bytes, uint32_t *d_n_frames,
+                             uint32_t *d_n_bad, uint32_t *d_dropped, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",

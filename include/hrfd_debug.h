@@ -89,6 +89,17 @@ int hrfd_afskgen_debug_slow(const hrfd_afskgen_message *msgs, const uint8_t *bit
                             uint32_t n_msgs, uint64_t N, const int16_t *pcm, uint32_t n_blocks, int16_t *out, uint8_t *active,
                             uint64_t *clips);
 
+/* the HDLC bank's law as the host states it (hrfd_hdlc.h), no device needed; host pointers.
+ *   slow:    the contract's loop over ONE channel and one call.  limits3 = {min_payload, max_payload, require_carrier}; bits
+ *            [n_bits] (0..2^20; may be NULL for 0); state260: the channel's 260 dwords (ones, in_frame, n, 0, the partial
+ *            frame), zero for a fresh channel, read and replaced; out [out_bytes] and counts3 = {n_frames, n_bad, dropped} as
+ *            hrfd_hdlc_process gives them for the channel.
+ *   max_out: hrfd_hdlc_max_out for limits given by value.
+ * tests/test_hdlc_model.py holds tests/hdlc_model.py against both. */
+int hrfd_hdlc_debug_slow(const uint32_t *limits3, const uint8_t *bits, uint32_t n_bits, uint32_t *state260, uint8_t *out,
+                         uint32_t out_bytes, uint32_t *counts3);
+int hrfd_hdlc_debug_max_out(uint32_t max_bits, uint32_t min_payload, uint32_t max_payload, uint32_t *out_bytes);
+
 /* ------------------------------------------------------------------ behaviour-changing hooks (HRFD_DEBUG_HOOKS=1) */
 int hrfd_rx_debug_set_atan(hrfd_rx *h, int mode);        /* -1 automatic, 0 table gather, 1 arithmetic */
 int hrfd_rx_debug_set_warm(hrfd_rx *h, int warm);        /* shrink the de-emphasis warm-up, seeds off: forces repairs */
