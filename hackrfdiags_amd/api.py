@@ -1340,50 +1340,20 @@ def _tonegen_segs(segs) -> np.ndarray:
     return np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 6)
 
 
-class ToneGen(_Bank):
-    """The tone generator bank (hrfd_tonegen_*): signalling on the PCM of n_channels transmit channels, the mirror of Tones.
-    Segments of one or two sines with a ramp of 8 ms at either end are queued on two tracks per channel at absolute stream
-    times and added, saturating, to the rows Mod and Duc.transmit read: DTMF digits, CTCSS sub-tones, tone bursts, paging
-    sequences.  Exact in integers on the detector's phase grid, and independent of how a stream is cut into calls.  (Its
-    kernel is one launch of at most 2^22 workgroups, so it has no chunked launch and no debug_set_max_wgs.)"""
-
-    _prefix = "tonegen"
-
-    def __init__(self, n_channels: int, device: int = -1):
-        self.n = int(n_channels)
-        self._create(self.n, device)
-
-    def queue(self, channel: int, track: int, segs, start: int = TONEGEN_APPEND):
-        """1..32 segments (gap, length, step_a, step_b, amp_a, amp_b; tonegen_segment makes one) on one track of one channel
-        or of all (ALL): the first begins at start + its gap, each next one its gap behind the end of the one before; start
-        TONEGEN_APPEND = max(time, the end of the track's last segment).  Refused whole if anything is out of order."""
-        a = _tonegen_segs(segs)
-        self._call("queue", int(channel), int(track), _ptr(a), a.shape[0], int(start))
-
-    def cut(self, channel: int = ALL, track: int = 0):
-        """ramp the segment in progress down over the next 64 samples and drop those not yet begun"""
-        self._call("cut", int(channel), int(track))
+class _GenBank(_Bank):
+    """What ToneGen and AfskGen share beyond _Bank: the clock, the clip counters and the process calls of a generator on
+    transmit PCM.  _max_blocks is the bank's limit on the blocks of a call."""
+    _max_blocks = 0
 
     def reset(self):
         """empty every queue, time = 0, clips = 0"""
         self._call("reset")
-
-    def set_time(self, N: int):
-        """move the clock only; the queues stay"""
-        self._call("set_time", int(N))
 
     def time(self) -> int:
         """the stream time of the next call's first sample"""
         v = C.c_uint64(0)
         self._call("time", C.byref(v))
         return int(v.value)
-
-    def pending(self, channel: int, track: int = 0):
-        """(segments of the track that have not ended, the end of the last of them: the time itself where there is none,
-        2^64 - 1 behind a FOREVER segment)"""
-        n, end = C.c_uint32(0), C.c_uint64(0)
-        self._call("pending", int(channel), int(track), C.byref(n), C.byref(end))
-        return int(n.value), int(end.value)
 
     def clips(self, channel: int) -> int:
         """samples of the channel the saturation changed, since create or reset; blocking"""
@@ -1405,8 +1375,8 @@ class ToneGen(_Bank):
         n_blocks = int(n_blocks)
         if n_blocks < 0 or n_blocks > 0xFFFFFFFF:
             raise ValueError(f"n_blocks {n_blocks}")
-        out = np.zeros((self.n, min(n_blocks, TONEGEN_MAX_BLOCKS), 512), dtype=np.int16)
-        active = np.zeros((self.n, min(n_blocks, TONEGEN_MAX_BLOCKS)), dtype=np.uint8) if want_active else None
+        out = np.zeros((self.n, min(n_blocks, self._max_blocks), 512), dtype=np.int16)
+        active = np.zeros((self.n, min(n_blocks, self._max_blocks)), dtype=np.uint8) if want_active else None
         self._call("process", _ptr(x), n_blocks, _ptr(out), _ptr(active))
         return (out, active) if want_active else out
 
@@ -1418,6 +1388,43 @@ class ToneGen(_Bank):
             out_stride = int(channel_stride) if in_place else 1024 * int(n_blocks)
         self._call("process_device", _ptr(d_pcm), int(channel_stride), int(n_blocks), _ptr(d_out), int(out_stride), _ptr(d_active),
                    _ptr(stream))
+
+
+class ToneGen(_GenBank):
+    """The tone generator bank (hrfd_tonegen_*): signalling on the PCM of n_channels transmit channels, the mirror of Tones.
+    Segments of one or two sines with a ramp of 8 ms at either end are queued on two tracks per channel at absolute stream
+    times and added, saturating, to the rows Mod and Duc.transmit read: DTMF digits, CTCSS sub-tones, tone bursts, paging
+    sequences.  Exact in integers on the detector's phase grid, and independent of how a stream is cut into calls.  (Its
+    kernel is one launch of at most 2^22 workgroups, so it has no chunked launch and no debug_set_max_wgs.)"""
+
+    _prefix = "tonegen"
+    _max_blocks = TONEGEN_MAX_BLOCKS
+
+    def __init__(self, n_channels: int, device: int = -1):
+        self.n = int(n_channels)
+        self._create(self.n, device)
+
+    def queue(self, channel: int, track: int, segs, start: int = TONEGEN_APPEND):
+        """1..32 segments (gap, length, step_a, step_b, amp_a, amp_b; tonegen_segment makes one) on one track of one channel
+        or of all (ALL): the first begins at start + its gap, each next one its gap behind the end of the one before; start
+        TONEGEN_APPEND = max(time, the end of the track's last segment).  Refused whole if anything is out of order."""
+        a = _tonegen_segs(segs)
+        self._call("queue", int(channel), int(track), _ptr(a), a.shape[0], int(start))
+
+    def cut(self, channel: int = ALL, track: int = 0):
+        """ramp the segment in progress down over the next 64 samples and drop those not yet begun"""
+        self._call("cut", int(channel), int(track))
+
+    def set_time(self, N: int):
+        """move the clock only; the queues stay"""
+        self._call("set_time", int(N))
+
+    def pending(self, channel: int, track: int = 0):
+        """(segments of the track that have not ended, the end of the last of them: the time itself where there is none,
+        2^64 - 1 behind a FOREVER segment)"""
+        n, end = C.c_uint32(0), C.c_uint64(0)
+        self._call("pending", int(channel), int(track), C.byref(n), C.byref(end))
+        return int(n.value), int(end.value)
 
     # ---- what the segments are for
     def dial(self, channel: int, keys: str, on_ms: float = 96, off_ms: float = 32, amplitude: int = 8000, track: int = 0,
@@ -1687,7 +1694,7 @@ def hdlc_encode(payloads, n_lead_flags: int = 12, n_between: int = 2, n_tail_fla
     return np.array(out, dtype=np.uint8)
 
 
-class AfskGen(_Bank):
+class AfskGen(_GenBank):
     """The AFSK generator bank (hrfd_afskgen_*): packet data on the PCM of n_channels transmit channels, the mirror of Afsk.
     Messages of up to 8192 bits, each with a modem of its own (Bell 202 by default), are queued per channel at absolute
     stream times, at most four that have not ended, and added, saturating, to the rows Mod and Duc.transmit read, as
@@ -1697,6 +1704,7 @@ class AfskGen(_Bank):
     debug_set_max_wgs.)"""
 
     _prefix = "afskgen"
+    _max_blocks = AFSKGEN_MAX_BLOCKS
 
     def __init__(self, n_channels: int, device: int = 0):
         self.n = int(n_channels)
@@ -1726,59 +1734,15 @@ class AfskGen(_Bank):
         """ramp the message in progress down over the next 64 samples and drop those not yet begun"""
         self._call("cut", int(channel))
 
-    def reset(self):
-        """empty every queue, time = 0, clips = 0"""
-        self._call("reset")
-
     def set_time(self, N: int):
         """move the clock; refused while a channel holds a message that has not ended"""
         self._call("set_time", int(N))
-
-    def time(self) -> int:
-        """the stream time of the next call's first sample"""
-        v = C.c_uint64(0)
-        self._call("time", C.byref(v))
-        return int(v.value)
 
     def pending(self, channel: int):
         """(messages of the channel that have not ended, the end of the last of them: the time itself where there is none)"""
         n, end = C.c_uint32(0), C.c_uint64(0)
         self._call("pending", int(channel), C.byref(n), C.byref(end))
         return int(n.value), int(end.value)
-
-    def clips(self, channel: int) -> int:
-        """samples of the channel the saturation changed, since create or reset; blocking"""
-        v = C.c_uint64(0)
-        self._call("get_clips", int(channel), C.byref(v))
-        return int(v.value)
-
-    def process(self, pcm, n_blocks: int = None, want_active: bool = False):
-        """pcm int16 [n_channels, n_blocks, 512], or None with n_blocks (generate only) -> out int16 [n_channels, n_blocks,
-        512], or (out, active uint8 [n_channels, n_blocks]) with want_active; blocking"""
-        x = None
-        if pcm is not None:
-            x = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.n, -1)
-            if x.shape[1] % 512 != 0 or (n_blocks is not None and x.shape[1] != 512 * int(n_blocks)):
-                raise ValueError(f"a channel's PCM must be whole blocks of 512 samples, got {x.shape[1]} samples")
-            n_blocks = x.shape[1] // 512
-        elif n_blocks is None:
-            raise ValueError("generate only needs n_blocks")
-        n_blocks = int(n_blocks)
-        if n_blocks < 0 or n_blocks > 0xFFFFFFFF:
-            raise ValueError(f"n_blocks {n_blocks}")
-        out = np.zeros((self.n, min(n_blocks, AFSKGEN_MAX_BLOCKS), 512), dtype=np.int16)
-        active = np.zeros((self.n, min(n_blocks, AFSKGEN_MAX_BLOCKS)), dtype=np.uint8) if want_active else None
-        self._call("process", _ptr(x), n_blocks, _ptr(out), _ptr(active))
-        return (out, active) if want_active else out
-
-    def process_device(self, d_pcm, channel_stride: int, n_blocks: int, d_out, out_stride: int = 0, d_active=None, stream=None):
-        """device pointers (ints); d_pcm None = generate only, d_active may be None; out_stride 0 = the input's stride where
-        d_out is d_pcm (in place), dense rows otherwise; asynchronous on stream (None = the handle's own)"""
-        if not out_stride:
-            in_place = d_pcm is not None and d_out is not None and _ptr(d_out).value == _ptr(d_pcm).value
-            out_stride = int(channel_stride) if in_place else 1024 * int(n_blocks)
-        self._call("process_device", _ptr(d_pcm), int(channel_stride), int(n_blocks), _ptr(d_out), int(out_stride), _ptr(d_active),
-                   _ptr(stream))
 
 
 class Engine:

@@ -52,9 +52,6 @@ static_assert(kAfskMaskDw * 4 == kAfskThreads, "a lane's eight decisions are one
 static_assert(kAfskLeadDw % 4 == 0, "the last lanes' own dwords are the next step's lead");
 static_assert(65536u <= kBankMaxWgs, "one workgroup per channel is one launch");
 
-typedef uint32_t afsk_u4 __attribute__((ext_vector_type(4)));
-typedef uint32_t afsk_u4_any __attribute__((ext_vector_type(4), aligned(2)));      // 16 bytes at any even address
-
 struct AfskParams
 {
   const int16_t *pcm;                      // [C] rows of n_blocks x 512 samples, stride bytes apart, even address
@@ -135,10 +132,10 @@ __global__ __launch_bounds__(kAfskThreads) void k_afsk(const AfskParams P)
   uint32_t h_prev = __builtin_amdgcn_readfirstlane(flags & 1u), last = __builtin_amdgcn_readfirstlane((flags >> 1) & 1u);
   uint32_t count = 0;
 
-  afsk_u4 next = {0u, 0u, 0u, 0u};
+  pcm_u4 next = {0u, 0u, 0u, 0u};
   if (tid * kAfskPer < n)
   {
-    next = *(const afsk_u4_any *)(row + tid * kAfskPer);
+    next = pcm_load8(row + tid * kAfskPer);
   }
   uint32_t m[4] = {0u, 0u, 0u, 0u};            // the lane's samples as the filter sees them
   uint32_t valid = 0;                          // samples of the step at hand
@@ -157,10 +154,10 @@ __global__ __launch_bounds__(kAfskThreads) void k_afsk(const AfskParams P)
         xs[4 * (tid - (kAfskThreads - kAfskLeadDw / 4)) + q] = m[q];
       }
     }
-    const afsk_u4 cur = next;
+    const pcm_u4 cur = next;
     if (at + kAfskStep < n)
     {
-      next = *(const afsk_u4_any *)(row + at + kAfskStep);
+      next = pcm_load8(row + at + kAfskStep);
     }
     const uint32_t d[4] = {cur.x, cur.y, cur.z, cur.w};
     const uint32_t pos = at % kAfskBlock, lim = active ? pcm_block_limit(n_row, at / kAfskBlock) : 0u;
@@ -360,15 +357,7 @@ extern "C" int hrfd_afsk_set_carrier(hrfd_afsk *a, uint64_t min_power)
   return HRFD_OK;
 }
 
-extern "C" int hrfd_afsk_reset(hrfd_afsk *a, uint32_t channel)
-{
-  BANK_TRY(hrfd::pcm_check_channel("hrfd_afsk_reset", channel, 65536));
-  BANK_TRY(hrfd::bank_need_handle("hrfd_afsk_reset", a));
-  BANK_TRY(hrfd::pcm_check_channel("hrfd_afsk_reset", channel, a->n_channels));
-  std::lock_guard<std::mutex> g(a->core.mu);
-  a->hist.mark(channel);
-  return HRFD_OK;
-}
+extern "C" int hrfd_afsk_reset(hrfd_afsk *a, uint32_t channel) { return hrfd::bank_reset_history(a, "hrfd_afsk_reset", channel); }
 
 extern "C" int hrfd_afsk_max_bits(hrfd_afsk *a, uint32_t n_blocks, uint32_t *max_bits)
 {

@@ -1,32 +1,27 @@
 // hackrfdiags_amd/csrc/hrfd_afskgen.h -- what the AFSK generator bank (hrfd_afskgen_*) needs no HIP for: the limits, the law
 // of one message (levels, length, the bit of a sample, the phase as a running sum), the rules of a channel's queue (laying a
 // message out, the merge with what is queued, the cut, dropping what has ended), the argument checks, and a slow loop over
-// one channel that restates the contract of include/hrfd.h sample by sample.  The sine index, the mix, the ramp and the
-// output are the tone generator's (hrfd_tonegen.h), used as they are.  Plain C++ like hrfd_tonegen.h
-// (tests/cpp/san_afskgen.cc compiles it on the CPU; hrfd_afskgen.hip includes it for the host side and the kernel); the
-// includer declares `int fail(int code, const char *fmt, ...)`, the HRFD_* codes, hrfd_tonegen_segment and
-// hrfd_afskgen_message first.
+// one channel that restates the contract of include/hrfd.h sample by sample.  The limits of a call, the sine index, the
+// mix, the ramp, the output and the checks of a time and of a process call are the ones it shares with the tone generator
+// (hrfd_gen.h).  Plain C++ like hrfd_tonegen.h (tests/cpp/san_afskgen.cc compiles it on the CPU; hrfd_afskgen.hip includes
+// it for the host side and the kernel); the includer declares `int fail(int code, const char *fmt, ...)`, the HRFD_* codes
+// and hrfd_afskgen_message first.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "hrfd_tonegen.h"
+#include "hrfd_gen.h"
 
 namespace hrfd {
 
-constexpr uint32_t kAfskgenBlock = kPcmBlock;
 constexpr uint32_t kAfskgenMaxMessages = 4;    // per channel, those that have not ended: the slots of the device's copy
 constexpr uint32_t kAfskgenMaxBits = 8192;     // data bits of one message
 constexpr uint32_t kAfskgenLevelWords = kAfskgenMaxBits / 32;     // 256 dwords = 1 KiB of levels a slot
-constexpr uint32_t kAfskgenMaxBlocks = 1024;
-constexpr uint32_t kAfskgenMaxAmp = kTonegenMaxAmp;
 constexpr uint32_t kAfskgenMaxStep = 1u << 31;
 constexpr uint32_t kAfskgenNrzi = 1u;          // bit 0 of a message's flags
-constexpr uint64_t kAfskgenAppend = ~0ull;
 constexpr uint64_t kAfskgenMaxLength = 1ull << 31;     // L stays below this: k fits 31 bits
-constexpr uint64_t kAfskgenMaxTime = kTonegenMaxTime;
 
 // one message as the kernel reads it (32 bytes): it sounds at stream times start <= n < end.  A cut moves the end in front
 // of start + L; all zeros is an empty slot (no end lies above a stream time)
@@ -119,8 +114,8 @@ inline uint32_t afskgen_theta_at(const AfskgenSlot &s, const uint32_t *levels, u
 HRFD_PCM_HD int32_t afskgen_sample(const AfskgenSlot &s, uint64_t n, uint32_t theta, const int16_t *cos_table)
 {
   const uint64_t k = n - s.start, left = s.end - n;
-  const int32_t v = tonegen_mix(s.amp, cos_table[tonegen_sin_index(theta)], 0u, 0);
-  return tonegen_ramp(v, (uint32_t)(k < kTonegenRamp ? k + 1 : kTonegenRamp), (uint32_t)(left < kTonegenRamp ? left : kTonegenRamp));
+  const int32_t v = gen_mix(s.amp, cos_table[gen_sin_index(theta)], 0u, 0);
+  return gen_ramp(v, (uint32_t)(k < kGenRamp ? k + 1 : kGenRamp), (uint32_t)(left < kGenRamp ? left : kGenRamp));
 }
 
 // ---- the queue of one channel
@@ -168,9 +163,9 @@ inline int afskgen_check_message(const char *who, const hrfd_afskgen_message *ms
       return fail(HRFD_EINVAL, "%s: %s must be 1..2^31 (got %u)", who, names[i], steps[i]);
     }
   }
-  if (msg->amp > kAfskgenMaxAmp)
+  if (msg->amp > kGenMaxAmp)
   {
-    return fail(HRFD_EINVAL, "%s: amp above %u (%u)", who, kAfskgenMaxAmp, msg->amp);
+    return fail(HRFD_EINVAL, "%s: amp above %u (%u)", who, kGenMaxAmp, msg->amp);
   }
   if ((msg->flags & ~kAfskgenNrzi) != 0 || msg->pad != 0)
   {
@@ -179,16 +174,14 @@ inline int afskgen_check_message(const char *who, const hrfd_afskgen_message *ms
   return afskgen_length(who, msg->n_bits, msg->baud_step, L);
 }
 
-inline int afskgen_check_time(const char *who, uint64_t N) { return tonegen_check_time(who, N); }
-
-// The message laid out from `start` (kAfskgenAppend: max(N, the end of the channel's last message)) against what `q` holds
+// The message laid out from `start` (kGenAppend: max(N, the end of the channel's last message)) against what `q` holds
 // that has not ended at N: *slot is the message as it would be queued.  Refused, with `q` as it was: a start before N, an
 // overlap, a fifth message that has not ended, a time at or above 2^63.  msg has passed afskgen_check_message, which gave L
 inline int afskgen_lay_out(const char *who, const AfskgenQueue &q, uint64_t N, const hrfd_afskgen_message *msg, uint64_t L,
                            uint64_t start, AfskgenSlot *slot)
 {
   uint64_t at;
-  if (start == kAfskgenAppend)
+  if (start == kGenAppend)
   {
     afskgen_count_pending(q, N, &at);                      // N where nothing is pending
   }
@@ -209,7 +202,7 @@ inline int afskgen_lay_out(const char *who, const AfskgenQueue &q, uint64_t N, c
   s.space_step = msg->space_step;
   s.baud_step = msg->baud_step;
   s.amp = msg->amp;
-  if (at >= kAfskgenMaxTime || s.start >= kAfskgenMaxTime || s.end >= kAfskgenMaxTime)
+  if (at >= kGenMaxTime || s.start >= kGenMaxTime || s.end >= kGenMaxTime)
   {
     return fail(HRFD_EINVAL, "%s: the message would lie at or above stream time 2^63", who);
   }
@@ -265,7 +258,7 @@ inline void afskgen_cut(AfskgenQueue &q, uint64_t N)
   q.erase(std::remove_if(q.begin(), q.end(), [N](const AfskgenMsg &m) { return m.s.start > N; }), q.end());
   for (AfskgenMsg &m : q)
   {
-    m.s.end = std::min(m.s.end, N + kTonegenRamp);
+    m.s.end = std::min(m.s.end, N + kGenRamp);
   }
 }
 
@@ -276,7 +269,7 @@ inline void afskgen_cut(AfskgenQueue &q, uint64_t N)
 inline uint64_t afskgen_channel_slow(const int16_t *pcm_row, uint32_t n_blocks, const AfskgenSlot *msgs, const uint32_t *const *levels,
                                      uint32_t n_msgs, uint64_t N, const int16_t *cos_table, int16_t *out, uint8_t *active)
 {
-  const uint64_t n = (uint64_t)n_blocks * kAfskgenBlock;
+  const uint64_t n = (uint64_t)n_blocks * kGenBlock;
   if (out != pcm_row)
   {
     for (uint64_t i = 0; i < n; i++)
@@ -288,7 +281,7 @@ inline uint64_t afskgen_channel_slow(const int16_t *pcm_row, uint32_t n_blocks, 
   {
     for (uint32_t b = 0; b < n_blocks; b++)
     {
-      const uint64_t b0 = N + (uint64_t)b * kAfskgenBlock, b1 = b0 + kAfskgenBlock;
+      const uint64_t b0 = N + (uint64_t)b * kGenBlock, b1 = b0 + kGenBlock;
       active[b] = 0;
       for (uint32_t j = 0; j < n_msgs; j++)
       {
@@ -309,7 +302,7 @@ inline uint64_t afskgen_channel_slow(const int16_t *pcm_row, uint32_t n_blocks, 
     for (uint64_t t = first; t < last; t++)
     {
       bool clipped;
-      out[t - N] = (int16_t)tonegen_output(out[t - N], afskgen_sample(s, t, theta, cos_table), &clipped);
+      out[t - N] = (int16_t)gen_output(out[t - N], afskgen_sample(s, t, theta, cos_table), &clipped);
       clips += clipped ? 1 : 0;
       theta += afskgen_step(s, levels[j], (uint32_t)(t - s.start));
     }
@@ -319,12 +312,5 @@ inline uint64_t afskgen_channel_slow(const int16_t *pcm_row, uint32_t n_blocks, 
 
 // ---- the checks, each under `who`, the public function's name
 inline int afskgen_check_create(const char *who, uint32_t n_channels, const void *out) { return pcm_check_channels(who, n_channels, out); }
-
-// a process call's sizes and addresses: the tone generator's rules
-inline int afskgen_check_call(const char *who, const void *pcm, uint64_t in_stride, bool device_entry, uint32_t n_blocks,
-                              const void *out, uint64_t out_stride, uint32_t n_channels)
-{
-  return tonegen_check_call(who, pcm, in_stride, device_entry, n_blocks, out, out_stride, n_channels);
-}
 
 } // namespace hrfd

@@ -4,8 +4,9 @@
 //
 // PCM rows [C][n_blocks][512] int16 in (or none: generate only), the same rows with the messages added out, clips per
 // channel and, optionally, in which blocks a message sounds.  Exact integer arithmetic on the tone generator's phase grid,
-// contract in include/hrfd.h; tests/afskgen_model.py restates it in numpy, hrfd_afskgen.h holds the laws and the queue rules
-// both sides of this file share.
+// contract in include/hrfd.h; tests/afskgen_model.py restates it in numpy, hrfd_gen.h and hrfd_afskgen.h hold the laws and
+// the queue rules both sides of this file share.  The clock, the clip counters, the sine table and the process entries are
+// GenCore's (hrfd_bank.hip); the queues, their copy on the device and the launch are this file's.
 //
 // The handle keeps the queues on the host (at most 4 messages per channel that have not ended, absolute stream times) and a
 // copy on the device: per channel 4 slots of 32 bytes and 4 x 256 dwords of levels, 4 KiB of levels a channel, 256 MiB at
@@ -47,12 +48,9 @@ constexpr int kAfskgenPer = 8;                             // consecutive sample
 constexpr int kAfskgenTile = kAfskgenThreads * kAfskgenPer;        // 2048 samples
 constexpr int kAfskgenWaves = kAfskgenThreads / 64;
 constexpr uint32_t kAfskgenStageSlots = 256;               // (channel, slot) pairs of one upload from the pinned staging
-static_assert(kAfskgenTile / (int)kAfskgenBlock == kAfskgenWaves, "one wave per block of a tile");
+static_assert(kAfskgenTile / (int)kGenBlock == kAfskgenWaves, "one wave per block of a tile");
 static_assert(65536u <= kBankMaxWgs, "the grid is one launch");
 static_assert(kAfskgenPer * 1ull * kAfskgenMaxStep / (1ull << 32) + 1 < 32, "the bits of a lane's samples lie in two level words");
-
-typedef uint32_t afskgen_u4 __attribute__((ext_vector_type(4)));
-typedef uint32_t afskgen_u4_any __attribute__((ext_vector_type(4), aligned(2)));       // 16 bytes at any even address
 
 struct AfskgenParams
 {
@@ -82,7 +80,7 @@ __global__ __launch_bounds__(kAfskgenThreads) void k_afskgen(const AfskgenParams
   __shared__ int16_t sl[4096];
   __shared__ uint32_t totals[2][kAfskgenWaves];
   const uint32_t tid = threadIdx.x, c = blockIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint32_t n = P.n_blocks * kAfskgenBlock;
+  const uint32_t n = P.n_blocks * kGenBlock;
   const uint64_t call_end = P.N + n;
   const int16_t *row = P.pcm != nullptr ? (const int16_t *)((const char *)P.pcm + (uint64_t)c * P.stride) : nullptr;
   int16_t *orow = (int16_t *)((char *)P.out + (uint64_t)c * P.out_stride);
@@ -100,8 +98,8 @@ __global__ __launch_bounds__(kAfskgenThreads) void k_afskgen(const AfskgenParams
   uint32_t carry = 0;                      // theta of the message in progress at the tile's first sample
   if (row_busy)
   {
-    const afskgen_u4 *src = (const afskgen_u4 *)sine;
-    afskgen_u4 *dst = (afskgen_u4 *)sl;
+    const pcm_u4 *src = (const pcm_u4 *)sine;
+    pcm_u4 *dst = (pcm_u4 *)sl;
     dst[tid] = src[tid];
     dst[tid + kAfskgenThreads] = src[tid + kAfskgenThreads];
     carry = P.anchor[c];
@@ -120,13 +118,13 @@ __global__ __launch_bounds__(kAfskgenThreads) void k_afskgen(const AfskgenParams
     if (P.active != nullptr)
     {
       // wave w: block w of the tile
-      const uint64_t b0 = n0 + wave * kAfskgenBlock;
-      const uint32_t b = t0 / kAfskgenBlock + wave;
+      const uint64_t b0 = n0 + wave * kGenBlock;
+      const uint32_t b = t0 / kGenBlock + wave;
       bool sounds = false;
 #pragma unroll
       for (uint32_t j = 0; j < kAfskgenMaxMessages; j++)
       {
-        sounds = sounds || (slot[j].start < b0 + kAfskgenBlock && slot[j].end > b0);
+        sounds = sounds || (slot[j].start < b0 + kGenBlock && slot[j].end > b0);
       }
       if (lane == 0 && b < P.n_blocks)
       {
@@ -212,8 +210,8 @@ __global__ __launch_bounds__(kAfskgenThreads) void k_afskgen(const AfskgenParams
           const int32_t up = up0 + i, down = down0 - i;
           if (up >= 1 && left0 - i >= 1)
           {
-            const int32_t v = tonegen_mix(s.amp, sl[tonegen_cos_index(theta)], 0u, 0);
-            g[i] += tonegen_ramp(v, (uint32_t)up, (uint32_t)down);
+            const int32_t v = gen_mix(s.amp, sl[gen_cos_index(theta)], 0u, 0);
+            g[i] += gen_ramp(v, (uint32_t)up, (uint32_t)down);
           }
           theta += st[i];
         }
@@ -224,14 +222,14 @@ __global__ __launch_bounds__(kAfskgenThreads) void k_afskgen(const AfskgenParams
     {
       continue;                                            // (behind the passes: every lane has met their barriers)
     }
-    afskgen_u4 cur = {0u, 0u, 0u, 0u};
+    pcm_u4 cur = {0u, 0u, 0u, 0u};
     if (row != nullptr)
     {
-      cur = *(const afskgen_u4_any *)(row + at);
+      cur = pcm_load8(row + at);
     }
     if (!tile_hit)
     {
-      *(afskgen_u4_any *)(orow + at) = cur;                // a copy, or zeros
+      pcm_store8(orow + at, cur);                          // a copy, or zeros
       continue;
     }
     const uint32_t d[4] = {cur.x, cur.y, cur.z, cur.w};
@@ -241,15 +239,15 @@ __global__ __launch_bounds__(kAfskgenThreads) void k_afskgen(const AfskgenParams
     {
       const int32_t x = (i & 1) ? (int32_t)d[i / 2] >> 16 : (int32_t)(int16_t)d[i / 2];
       bool clip;
-      y[i] = (uint32_t)tonegen_output(x, g[i], &clip);
+      y[i] = (uint32_t)gen_output(x, g[i], &clip);
       clipped += clip ? 1u : 0u;
     }
-    afskgen_u4 v;
+    pcm_u4 v;
     v.x = (y[0] & 0xffffu) | (y[1] << 16);
     v.y = (y[2] & 0xffffu) | (y[3] << 16);
     v.z = (y[4] & 0xffffu) | (y[5] << 16);
     v.w = (y[6] & 0xffffu) | (y[7] << 16);
-    *(afskgen_u4_any *)(orow + at) = v;
+    pcm_store8(orow + at, v);
   }
 
   // the message in progress where the call ends: its theta there, for the next call
@@ -277,28 +275,20 @@ __global__ __launch_bounds__(kAfskgenThreads) void k_afskgen(const AfskgenParams
 struct hrfd_afskgen
 {
   hrfd::BankCore core;
+  hrfd::GenCore gen;                       // the clock, the clips, the sine table, the host path's staging
   uint32_t n_channels = 0;
 
   // host records, under core.mu
-  uint64_t N = 0;                          // the stream time of the next call's first sample
   std::vector<hrfd::AfskgenQueue> queue;   // [C]
-  uint64_t next_end = ~0ull;               // no message ends before this: a call below it has nothing to drop
   std::vector<uint8_t> dirty;              // [4][C]: 0 = as on the device, 1 = the slot differs, 2 = the slot and its levels
   std::vector<uint32_t> dirty_ids;         // the indices of the entries above that are not 0
   bool clear_slots = false;                // reset: the device's slots are zeroed ahead of the next launch
-  bool clear_clips = false;                // reset: the counters as well
 
   hrfd::PinnedBuf<hrfd::AfskgenSlot> h_slots;      // [256]
   hrfd::PinnedBuf<uint32_t> h_levels;      // [256][256]
   hrfd::DevBuf<hrfd::AfskgenSlot> d_slots; // [4][C]
   hrfd::DevBuf<uint32_t> d_levels;         // [4][C][256]
   hrfd::DevBuf<uint32_t> d_anchor;         // [C]
-  hrfd::DevBuf<int16_t> d_sine;            // [4096]
-  hrfd::DevBuf<unsigned long long> d_clips;        // [C]
-
-  // host-path staging
-  hrfd::DevBuf<int16_t> d_pcm, d_out;
-  hrfd::DevBuf<uint8_t> d_active;
 
   void touch(uint32_t c, uint32_t slot, uint8_t what)
   {
@@ -326,24 +316,24 @@ struct hrfd_afskgen
   // what has ended at N leaves the queues; its slots are emptied on the device, so that a clock set back finds nothing
   void drop_ended()
   {
-    if (next_end > N)
+    if (gen.next_end > gen.N)
     {
       return;
     }
-    next_end = ~0ull;
+    gen.next_end = ~0ull;
     for (uint32_t c = 0; c < n_channels; c++)
     {
       for (const hrfd::AfskgenMsg &m : queue[c])
       {
-        if (m.s.end <= N)
+        if (m.s.end <= gen.N)
         {
           touch(c, m.slot, 1);
         }
       }
-      hrfd::afskgen_drop_ended(queue[c], N);
+      hrfd::afskgen_drop_ended(queue[c], gen.N);
       for (const hrfd::AfskgenMsg &m : queue[c])
       {
-        next_end = std::min(next_end, m.s.end);
+        gen.next_end = std::min(gen.next_end, m.s.end);
       }
     }
   }
@@ -363,18 +353,11 @@ extern "C" int hrfd_afskgen_create(uint32_t n_channels, int device, hrfd_afskgen
   t->n_channels = n_channels;
   t->queue.resize(C);
   t->dirty.assign(S * C, 0);
-  std::vector<int16_t> sine(4096);
-  for (uint32_t i = 0; i < 4096; i++)
-  {
-    sine[i] = Q_DDC_COS[(i - 1024u) & 4095u];
-  }
-  if (!(t->d_slots.alloc(S * C) && t->d_levels.alloc(S * C * kAfskgenLevelWords) && t->d_anchor.alloc(C) && t->d_sine.alloc(4096) &&
-        t->d_clips.alloc(C) && t->h_slots.alloc(kAfskgenStageSlots) && t->h_levels.alloc((size_t)kAfskgenStageSlots * kAfskgenLevelWords) &&
-        hipMemcpy(t->d_sine, sine.data(), sizeof(int16_t) * 4096, hipMemcpyHostToDevice) == hipSuccess &&
+  if (!(t->d_slots.alloc(S * C) && t->d_levels.alloc(S * C * kAfskgenLevelWords) && t->d_anchor.alloc(C) &&
+        t->h_slots.alloc(kAfskgenStageSlots) && t->h_levels.alloc((size_t)kAfskgenStageSlots * kAfskgenLevelWords) && t->gen.alloc(C) &&
         hipMemset(t->d_slots, 0, sizeof(AfskgenSlot) * S * C) == hipSuccess &&
         hipMemset(t->d_levels, 0, sizeof(uint32_t) * S * C * kAfskgenLevelWords) == hipSuccess &&
-        hipMemset(t->d_anchor, 0, sizeof(uint32_t) * C) == hipSuccess &&
-        hipMemset(t->d_clips, 0, sizeof(unsigned long long) * C) == hipSuccess))
+        hipMemset(t->d_anchor, 0, sizeof(uint32_t) * C) == hipSuccess))
   {
     (void)hipGetLastError();
     bank_free(t);
@@ -400,9 +383,9 @@ extern "C" int hrfd_afskgen_queue(hrfd_afskgen *t, uint32_t channel, const hrfd_
   uint64_t L = 0;
   BANK_TRY(afskgen_check_message(who, msg, bits, &L));
   BANK_TRY(pcm_check_channel(who, channel, 65536));
-  if (start != kAfskgenAppend)
+  if (start != kGenAppend)
   {
-    BANK_TRY(afskgen_check_time(who, start));
+    BANK_TRY(gen_check_time(who, start));
   }
   BANK_TRY(bank_need_handle(who, t));
   BANK_TRY(pcm_check_channel(who, channel, t->n_channels));
@@ -414,14 +397,14 @@ extern "C" int hrfd_afskgen_queue(hrfd_afskgen *t, uint32_t channel, const hrfd_
   std::vector<AfskgenSlot> laid(last - first);
   for (uint32_t c = first; c < last; c++)
   {
-    BANK_TRY(afskgen_lay_out(who, t->queue[c], t->N, msg, L, start, &laid[c - first]));
+    BANK_TRY(afskgen_lay_out(who, t->queue[c], t->gen.N, msg, L, start, &laid[c - first]));
   }
   t->drop_ended();
   for (uint32_t c = first; c < last; c++)
   {
-    afskgen_drop_ended(t->queue[c], t->N);                 // (drop_ended has, unless nothing was due)
+    afskgen_drop_ended(t->queue[c], t->gen.N);                 // (drop_ended has, unless nothing was due)
     const uint32_t slot = afskgen_insert(t->queue[c], laid[c - first], std::vector<uint32_t>(levels));
-    t->next_end = std::min(t->next_end, laid[c - first].end);
+    t->gen.next_end = std::min(t->gen.next_end, laid[c - first].end);
     t->touch(c, slot, 2);
   }
   return HRFD_OK;
@@ -441,10 +424,10 @@ extern "C" int hrfd_afskgen_cut(hrfd_afskgen *t, uint32_t channel)
     {
       t->touch(c, m.slot, 1);
     }
-    afskgen_cut(q, t->N);
+    afskgen_cut(q, t->gen.N);
     for (const AfskgenMsg &m : q)
     {
-      t->next_end = std::min(t->next_end, m.s.end);
+      t->gen.next_end = std::min(t->gen.next_end, m.s.end);
     }
   });
   return HRFD_OK;
@@ -458,48 +441,36 @@ extern "C" int hrfd_afskgen_reset(hrfd_afskgen *t)
   {
     q.clear();
   }
-  t->N = 0;
-  t->next_end = ~0ull;
+  t->gen.reset();
   for (uint32_t id : t->dirty_ids)
   {
     t->dirty[id] = 0;
   }
   t->dirty_ids.clear();
   t->clear_slots = true;
-  t->clear_clips = true;
   return HRFD_OK;
 }
 
 extern "C" int hrfd_afskgen_set_time(hrfd_afskgen *t, uint64_t N)
 {
   using namespace hrfd;
-  BANK_TRY(afskgen_check_time("hrfd_afskgen_set_time", N));
+  BANK_TRY(gen_check_time("hrfd_afskgen_set_time", N));
   BANK_TRY(bank_need_handle("hrfd_afskgen_set_time", t));
   std::lock_guard<std::mutex> g(t->core.mu);
   for (uint32_t c = 0; c < t->n_channels; c++)
   {
-    if (afskgen_count_pending(t->queue[c], t->N, nullptr) != 0)
+    if (afskgen_count_pending(t->queue[c], t->gen.N, nullptr) != 0)
     {
       return fail(HRFD_EINVAL, "hrfd_afskgen_set_time: channel %u holds a message that has not ended (a clock that jumps into a "
                                "message would need its phase there)", c);
     }
   }
   t->drop_ended();
-  t->N = N;
+  t->gen.N = N;
   return HRFD_OK;
 }
 
-extern "C" int hrfd_afskgen_time(hrfd_afskgen *t, uint64_t *N)
-{
-  if (N == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_afskgen_time: NULL result");
-  }
-  BANK_TRY(hrfd::bank_need_handle("hrfd_afskgen_time", t));
-  std::lock_guard<std::mutex> g(t->core.mu);
-  *N = t->N;
-  return HRFD_OK;
-}
+extern "C" int hrfd_afskgen_time(hrfd_afskgen *t, uint64_t *N) { return hrfd::gen_time(t, "hrfd_afskgen_time", N); }
 
 extern "C" int hrfd_afskgen_pending(hrfd_afskgen *t, uint32_t channel, uint32_t *n_messages, uint64_t *end)
 {
@@ -513,15 +484,11 @@ extern "C" int hrfd_afskgen_pending(hrfd_afskgen *t, uint32_t channel, uint32_t 
   {
     return fail(HRFD_EINVAL, "%s: NULL results", who);
   }
-  BANK_TRY(bank_need_handle(who, t));
-  if (channel >= t->n_channels)
-  {
-    return fail(HRFD_EINVAL, "%s: channel %u (0..%u)", who, channel, t->n_channels - 1);
-  }
+  BANK_TRY(gen_check_getter(t, who, channel));
   std::lock_guard<std::mutex> g(t->core.mu);
   // counted without dropping: what has ended leaves the queue with the next call
   uint64_t last = 0;
-  const uint32_t count = afskgen_count_pending(t->queue[channel], t->N, &last);
+  const uint32_t count = afskgen_count_pending(t->queue[channel], t->gen.N, &last);
   if (n_messages != nullptr)
   {
     *n_messages = count;
@@ -535,42 +502,7 @@ extern "C" int hrfd_afskgen_pending(hrfd_afskgen *t, uint32_t channel, uint32_t 
 
 extern "C" int hrfd_afskgen_get_clips(hrfd_afskgen *t, uint32_t channel, uint64_t *n)
 {
-  using namespace hrfd;
-  const char *who = "hrfd_afskgen_get_clips";
-  if (n == nullptr || channel >= 65536)
-  {
-    return fail(HRFD_EINVAL, "%s: channel %u (one channel) and a result pointer", who, channel);
-  }
-  BANK_TRY(bank_need_handle(who, t));
-  if (channel >= t->n_channels)
-  {
-    return fail(HRFD_EINVAL, "%s: channel %u (0..%u)", who, channel, t->n_channels - 1);
-  }
-  {
-    std::lock_guard<std::mutex> g(t->core.mu);
-    if (t->clear_clips)
-    {
-      *n = 0;                              // reset, and no call since
-      return HRFD_OK;
-    }
-  }
-  HIP_TRY(hipSetDevice(t->core.device));
-  BANK_TRY(t->core.drain());
-  unsigned long long v = 0;
-  HIP_TRY(hipMemcpy(&v, t->d_clips + channel, sizeof(v), hipMemcpyDeviceToHost));
-  *n = v;
-  return HRFD_OK;
-}
-
-static int afskgen_check_process(hrfd_afskgen *t, const char *who, const void *pcm, uint64_t stride, bool device_entry,
-                                 uint32_t n_blocks, const void *out, uint64_t out_stride)
-{
-  // what the sizes and addresses decide on their own comes first, so that it is refused with its own text
-  BANK_TRY(hrfd::afskgen_check_call(who, pcm, stride, device_entry, n_blocks, out, out_stride, 1));
-  BANK_TRY(hrfd::bank_need_handle(who, t));
-  BANK_TRY(hrfd::afskgen_check_call(who, pcm, stride, device_entry, n_blocks, out, out_stride, t->n_channels));
-  std::lock_guard<std::mutex> g(t->core.mu);
-  return hrfd::afskgen_check_time(who, t->N + (uint64_t)hrfd::kAfskgenBlock * n_blocks - 1);       // the call's last sample
+  return hrfd::gen_get_clips(t, "hrfd_afskgen_get_clips", channel, n);
 }
 
 // the dirty (channel, slot) pairs from the host's queues to the device's copy, in runs of neighbouring entries that need the
@@ -627,12 +559,12 @@ static int afskgen_launch(hrfd_afskgen *t, const int16_t *d_pcm, uint64_t stride
                           uint64_t out_stride, uint8_t *d_active, hipStream_t st)
 {
   using namespace hrfd;
-  const uint64_t n = (uint64_t)kAfskgenBlock * n_blocks;
+  const uint64_t n = (uint64_t)kGenBlock * n_blocks;
   AfskgenParams P;
   BANK_TRY(t->core.order_behind_last(st));
   {
     std::lock_guard<std::mutex> g(t->core.mu);
-    P.N = t->N;
+    P.N = t->gen.N;
     if (t->clear_slots)
     {
       // behind a reset: empty slots, then what has been queued since
@@ -644,12 +576,7 @@ static int afskgen_launch(hrfd_afskgen *t, const int16_t *d_pcm, uint64_t stride
     {
       BANK_TRY(afskgen_stage(t, st));
     }
-    if (t->clear_clips)
-    {
-      HIP_TRY(hipMemsetAsync(t->d_clips, 0, sizeof(unsigned long long) * t->n_channels, st));
-      t->clear_clips = false;
-    }
-    t->N += n;
+    BANK_TRY(t->gen.advance(t->n_channels, n, st));
   }
   P.pcm = d_pcm;
   P.stride = stride;
@@ -658,11 +585,11 @@ static int afskgen_launch(hrfd_afskgen *t, const int16_t *d_pcm, uint64_t stride
   P.slots = t->d_slots;
   P.levels = t->d_levels;
   P.anchor = t->d_anchor;
-  P.clips = t->d_clips;
+  P.clips = t->gen.d_clips;
   P.active = d_active;
   P.n_blocks = n_blocks;
   P.n_channels = t->n_channels;
-  hipLaunchKernelGGL(k_afskgen, dim3(t->n_channels), dim3(kAfskgenThreads), 0, st, P, (const int16_t *)t->d_sine.p);
+  hipLaunchKernelGGL(k_afskgen, dim3(t->n_channels), dim3(kAfskgenThreads), 0, st, P, (const int16_t *)t->gen.d_sine.p);
   BANK_TRY(bank_launch_ok("k_afskgen"));
   t->core.launched_on(st);
   return HRFD_OK;
@@ -671,26 +598,13 @@ static int afskgen_launch(hrfd_afskgen *t, const int16_t *d_pcm, uint64_t stride
 extern "C" int hrfd_afskgen_process_device(hrfd_afskgen *t, const int16_t *d_pcm, uint64_t channel_stride_bytes, uint32_t n_blocks,
                                            int16_t *d_out, uint64_t out_stride_bytes, uint8_t *d_active, void *stream)
 {
-  BANK_TRY(afskgen_check_process(t, "hrfd_afskgen_process_device", d_pcm, channel_stride_bytes, true, n_blocks, d_out,
-                                 out_stride_bytes));
-  HIP_TRY(hipSetDevice(t->core.device));
-  return afskgen_launch(t, d_pcm, channel_stride_bytes, n_blocks, d_out, out_stride_bytes, d_active, t->core.stream_or_own(stream));
+  return hrfd::gen_process_device(t, "hrfd_afskgen_process_device", afskgen_launch, d_pcm, channel_stride_bytes, n_blocks, d_out,
+                                  out_stride_bytes, d_active, stream);
 }
 
 extern "C" int hrfd_afskgen_process(hrfd_afskgen *t, const int16_t *pcm, uint32_t n_blocks, int16_t *out, uint8_t *active)
 {
-  using namespace hrfd;
-  BANK_TRY(afskgen_check_process(t, "hrfd_afskgen_process", pcm, 0, false, n_blocks, out, 0));
-  BankHostCall call(t->core);
-  const size_t C = t->n_channels, row = 2 * (size_t)kAfskgenBlock * n_blocks;
-  const int16_t *d_pcm = call.up(t->d_pcm, pcm, row * C);
-  int16_t *d_out = call.room(t->d_out, out, row * C);
-  uint8_t *d_active = call.room(t->d_active, active, C * n_blocks);
-  BANK_TRY(call.rc);
-  BANK_TRY(afskgen_launch(t, d_pcm, row, n_blocks, d_out, row, d_active, call.st));
-  call.down(out, d_out, row * C);
-  call.down(active, d_active, C * n_blocks);
-  return call.finish();
+  return hrfd::gen_process(t, "hrfd_afskgen_process", afskgen_launch, pcm, n_blocks, out, active);
 }
 
 // ---- host-only debug entries (include/hrfd_debug.h): the laws of hrfd_afskgen.h, no device
@@ -720,9 +634,9 @@ extern "C" int hrfd_afskgen_debug_slow(const hrfd_afskgen_message *msgs, const u
 {
   using namespace hrfd;
   const char *who = "hrfd_afskgen_debug_slow";
-  BANK_TRY(afskgen_check_call(who, pcm, 0, false, n_blocks, out, 0, 1));
-  BANK_TRY(afskgen_check_time(who, N));
-  BANK_TRY(afskgen_check_time(who, N + (uint64_t)kAfskgenBlock * n_blocks - 1));
+  BANK_TRY(gen_check_call(who, pcm, 0, false, n_blocks, out, 0, 1));
+  BANK_TRY(gen_check_time(who, N));
+  BANK_TRY(gen_check_time(who, N + (uint64_t)kGenBlock * n_blocks - 1));
   if (n_msgs > kAfskgenMaxMessages || (n_msgs != 0 && (msgs == nullptr || bits == nullptr || starts == nullptr)))
   {
     return fail(HRFD_EINVAL, "%s: at most %u messages, with their bits and starts (got %u)", who, kAfskgenMaxMessages, n_msgs);
@@ -734,7 +648,7 @@ extern "C" int hrfd_afskgen_debug_slow(const hrfd_afskgen_message *msgs, const u
   {
     uint64_t L = 0;
     BANK_TRY(afskgen_check_message(who, msgs + j, bits, &L));
-    BANK_TRY(afskgen_check_time(who, starts[j]));
+    BANK_TRY(gen_check_time(who, starts[j]));
     const AfskgenQueue none;
     BANK_TRY(afskgen_lay_out(who, none, 0, msgs + j, L, starts[j], &slots[j]));
     if (ends != nullptr && ends[j] < slots[j].end)

@@ -409,15 +409,7 @@ extern "C" int hrfd_audio_set_want(hrfd_audio *a, uint32_t channel, uint32_t wan
   return HRFD_OK;
 }
 
-extern "C" int hrfd_audio_reset(hrfd_audio *a, uint32_t channel)
-{
-  BANK_TRY(hrfd::pcm_check_channel("hrfd_audio_reset", channel, 65536));
-  BANK_TRY(hrfd::bank_need_handle("hrfd_audio_reset", a));
-  BANK_TRY(hrfd::pcm_check_channel("hrfd_audio_reset", channel, a->n_channels));
-  std::lock_guard<std::mutex> g(a->core.mu);
-  a->hist.mark(channel);
-  return HRFD_OK;
-}
+extern "C" int hrfd_audio_reset(hrfd_audio *a, uint32_t channel) { return hrfd::bank_reset_history(a, "hrfd_audio_reset", channel); }
 
 // test hook: the workgroups of one launch of k_audio_fir, 1 .. 2^22 (2^22 unless set)
 extern "C" int hrfd_audio_debug_set_max_wgs(hrfd_audio *a, uint32_t n)

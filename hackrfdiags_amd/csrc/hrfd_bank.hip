@@ -1,9 +1,10 @@
 // hackrfdiags_amd/csrc/hrfd_bank.hip -- the host core of the bank handles (hrfd_ddc, hrfd_duc, hrfd_spec, hrfd_cal,
 // hrfd_tone, hrfd_audio, hrfd_resamp, hrfd_level, hrfd_tonegen, hrfd_afsk, hrfd_afskgen, hrfd_hdlc) and of the transmit handles (hrfd_mod, hrfd_nco): device and stream ownership with the three ordering rules (BankCore), what stands
 // around every launch (the NULL-handle refusal, the launch check, the chunked launch, the loop over the selected channels),
-// the blocking host entry (BankHostCall), the history of the PCM banks (BankHistory), and the setters and argument checks
-// the DDC and the DUC share.  DESIGN.md 3.5a states the rules; hrfd_bank.h and hrfd_pcm.h hold the parts that need no HIP,
-// hrfd_buf.h the buffers a handle owns (DevBuf, PinnedBuf: shared with the receive and transmit handles).
+// the blocking host entry (BankHostCall), the history of the PCM banks (BankHistory) with the reset over it, the host part
+// of the two generator banks (GenCore: clock, clips, sine table, the process entries), and the setters and argument checks
+// the DDC and the DUC share.  DESIGN.md 3.5a states the rules; hrfd_bank.h, hrfd_pcm.h and hrfd_gen.h hold the parts that
+// need no HIP, hrfd_buf.h the buffers a handle owns (DevBuf, PinnedBuf: shared with the receive and transmit handles).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -12,8 +13,8 @@
 #include <mutex>
 #include <vector>
 
-#include "hrfd_bank.h"
 #include "hrfd_buf.h"
+#include "hrfd_gen.h"
 #include "hrfd_ddc_tables.h"
 
 namespace hrfd {
@@ -281,6 +282,151 @@ struct BankHistory
   uint32_t *out() const { return d_hist + (side ^ 1u) * C * dw; }
   void flip() { side ^= 1u; }
 };
+
+// hrfd_<bank>_reset of a bank whose history is a BankHistory `hist` (level, audio, afsk, hdlc): the channel, or all, starts
+// from zeros with the next launch
+template <class H>
+static int bank_reset_history(H *h, const char *who, uint32_t channel)
+{
+  BANK_TRY(pcm_check_channel(who, channel, 65536));
+  BANK_TRY(bank_need_handle(who, h));
+  BANK_TRY(pcm_check_channel(who, channel, h->n_channels));
+  std::lock_guard<std::mutex> g(h->core.mu);
+  h->hist.mark(channel);
+  return HRFD_OK;
+}
+
+// What a generator bank (hrfd_tonegen, hrfd_afskgen) keeps beside its BankCore: the clock, the watermark of its queues, the
+// clip counters with their lazy clear, the rotated sine table and the staging of the blocking host entry.  Host fields under
+// the handle's core.mu.  The queues, their copy on the device and the kernel are the bank's own: the gen_* functions below
+// take a handle H with core, n_channels and gen, and the bank's launch function
+//   int launch(H *, const int16_t *d_pcm, uint64_t stride, uint32_t n_blocks, int16_t *d_out, uint64_t out_stride,
+//              uint8_t *d_active, hipStream_t st)
+struct GenCore
+{
+  uint64_t N = 0;                          // the stream time of the next call's first sample
+  uint64_t next_end = ~0ull;               // nothing queued ends before this: a call below it has nothing to drop
+  bool clear_clips = false;                // reset: the counters are zeroed ahead of the next launch
+  DevBuf<int16_t> d_sine;                  // [4096]: sine[i] = COS[(i - 1024) & 4095]
+  DevBuf<unsigned long long> d_clips;      // [C]
+  DevBuf<int16_t> d_pcm, d_out;            // host-path staging
+  DevBuf<uint8_t> d_active;
+
+  bool alloc(size_t C)
+  {
+    std::vector<int16_t> sine(4096);
+    for (uint32_t i = 0; i < 4096; i++)
+    {
+      sine[i] = Q_DDC_COS[(i - 1024u) & 4095u];
+    }
+    return d_sine.alloc(4096) && d_clips.alloc(C) &&
+           hipMemcpy(d_sine, sine.data(), sizeof(int16_t) * 4096, hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemset(d_clips, 0, sizeof(unsigned long long) * C) == hipSuccess;
+  }
+
+  // the core's part of a reset, under mu; the bank empties its queues
+  void reset()
+  {
+    N = 0;
+    next_end = ~0ull;
+    clear_clips = true;
+  }
+
+  // the last step of a launch's part under mu, behind the bank's staging on `st`: the counters are zeroed if a reset asked
+  // for it, and the clock moves on by the call's n samples
+  int advance(uint32_t n_channels, uint64_t n, hipStream_t st)
+  {
+    if (clear_clips)
+    {
+      HIP_TRY(hipMemsetAsync(d_clips, 0, sizeof(unsigned long long) * n_channels, st));
+      clear_clips = false;
+    }
+    N += n;
+    return HRFD_OK;
+  }
+};
+
+template <class H>
+static int gen_time(H *h, const char *who, uint64_t *N)
+{
+  if (N == nullptr)
+  {
+    return fail(HRFD_EINVAL, "%s: NULL result", who);
+  }
+  BANK_TRY(bank_need_handle(who, h));
+  std::lock_guard<std::mutex> g(h->core.mu);
+  *N = h->gen.N;
+  return HRFD_OK;
+}
+
+// the handle and the channel of a getter of one channel (get_clips, pending), behind what its arguments decide on their own
+template <class H>
+static int gen_check_getter(H *h, const char *who, uint32_t channel)
+{
+  BANK_TRY(bank_need_handle(who, h));
+  return gen_check_one_channel(who, channel, h->n_channels);
+}
+
+template <class H>
+static int gen_get_clips(H *h, const char *who, uint32_t channel, uint64_t *n)
+{
+  if (n == nullptr || channel >= 65536)
+  {
+    return fail(HRFD_EINVAL, "%s: channel %u (one channel) and a result pointer", who, channel);
+  }
+  BANK_TRY(gen_check_getter(h, who, channel));
+  {
+    std::lock_guard<std::mutex> g(h->core.mu);
+    if (h->gen.clear_clips)
+    {
+      *n = 0;                              // reset, and no call since
+      return HRFD_OK;
+    }
+  }
+  HIP_TRY(hipSetDevice(h->core.device));
+  BANK_TRY(h->core.drain());
+  unsigned long long v = 0;
+  HIP_TRY(hipMemcpy(&v, h->gen.d_clips + channel, sizeof(v), hipMemcpyDeviceToHost));
+  *n = v;
+  return HRFD_OK;
+}
+
+template <class H>
+static int gen_check_process(H *h, const char *who, const void *pcm, uint64_t stride, bool device_entry, uint32_t n_blocks,
+                             const void *out, uint64_t out_stride)
+{
+  // what the sizes and addresses decide on their own comes first, so that it is refused with its own text
+  BANK_TRY(gen_check_call(who, pcm, stride, device_entry, n_blocks, out, out_stride, 1));
+  BANK_TRY(bank_need_handle(who, h));
+  BANK_TRY(gen_check_call(who, pcm, stride, device_entry, n_blocks, out, out_stride, h->n_channels));
+  std::lock_guard<std::mutex> g(h->core.mu);
+  return gen_check_time(who, h->gen.N + (uint64_t)kGenBlock * n_blocks - 1);       // the call's last sample
+}
+
+template <class H, class Launch>
+static int gen_process_device(H *h, const char *who, Launch launch, const int16_t *d_pcm, uint64_t stride, uint32_t n_blocks,
+                              int16_t *d_out, uint64_t out_stride, uint8_t *d_active, void *stream)
+{
+  BANK_TRY(gen_check_process(h, who, d_pcm, stride, true, n_blocks, d_out, out_stride));
+  HIP_TRY(hipSetDevice(h->core.device));
+  return launch(h, d_pcm, stride, n_blocks, d_out, out_stride, d_active, h->core.stream_or_own(stream));
+}
+
+template <class H, class Launch>
+static int gen_process(H *h, const char *who, Launch launch, const int16_t *pcm, uint32_t n_blocks, int16_t *out, uint8_t *active)
+{
+  BANK_TRY(gen_check_process(h, who, pcm, 0, false, n_blocks, out, 0));
+  BankHostCall call(h->core);
+  const size_t C = h->n_channels, row = 2 * (size_t)kGenBlock * n_blocks;
+  const int16_t *d_pcm = call.up(h->gen.d_pcm, pcm, row * C);
+  int16_t *d_out = call.room(h->gen.d_out, out, row * C);
+  uint8_t *d_active = call.room(h->gen.d_active, active, C * n_blocks);
+  BANK_TRY(call.rc);
+  BANK_TRY(launch(h, d_pcm, row, n_blocks, d_out, row, d_active, call.st));
+  call.down(out, d_out, row * C);
+  call.down(active, d_active, C * n_blocks);
+  return call.finish();
+}
 
 // The setters and getters of a handle with one tuning record per channel (the DDC and the DUC), under `who`, the public
 // function's name.  H has core, n_channels, n_captures, h_chan, N (the absolute wideband sample counter), dirty and

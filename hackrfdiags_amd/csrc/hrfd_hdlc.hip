@@ -418,15 +418,7 @@ extern "C" int hrfd_hdlc_set_require_carrier(hrfd_hdlc *h, int on)
   return HRFD_OK;
 }
 
-extern "C" int hrfd_hdlc_reset(hrfd_hdlc *h, uint32_t channel)
-{
-  BANK_TRY(hrfd::pcm_check_channel("hrfd_hdlc_reset", channel, 65536));
-  BANK_TRY(hrfd::bank_need_handle("hrfd_hdlc_reset", h));
-  BANK_TRY(hrfd::pcm_check_channel("hrfd_hdlc_reset", channel, h->n_channels));
-  std::lock_guard<std::mutex> g(h->core.mu);
-  h->hist.mark(channel);
-  return HRFD_OK;
-}
+extern "C" int hrfd_hdlc_reset(hrfd_hdlc *h, uint32_t channel) { return hrfd::bank_reset_history(h, "hrfd_hdlc_reset", channel); }
 
 extern "C" int hrfd_hdlc_max_out(hrfd_hdlc *h, uint32_t max_bits, uint32_t *out_bytes)
 {

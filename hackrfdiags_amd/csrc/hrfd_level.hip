@@ -48,9 +48,6 @@ static_assert(kLevelRing >= (int)kLevelHist + 2 * kLevelStepFrames && (kLevelRin
               "the next step's peaks fall on slots this step does not read");
 static_assert(65536u <= kBankMaxWgs, "one workgroup per channel is one launch");
 
-typedef uint32_t level_u4 __attribute__((ext_vector_type(4)));
-typedef uint32_t level_u4_any __attribute__((ext_vector_type(4), aligned(2)));      // 16 bytes at any even address
-
 struct LevelParams
 {
   const int16_t *pcm;                      // [C] rows of n_blocks x 512 samples, stride bytes apart, even address
@@ -68,9 +65,6 @@ struct LevelParams
 };
 
 // a lane's eight samples: the type promises an even address only, and the compiler picks what the target takes there
-__device__ __forceinline__ level_u4 level_load8(const int16_t *src) { return *(const level_u4_any *)src; }
-__device__ __forceinline__ void level_store8(int16_t *dst, level_u4 v) { *(level_u4_any *)dst = v; }
-
 // the maximum over the eight lanes of a frame (lanes 8 j .. 8 j + 7 of a wave)
 __device__ __forceinline__ uint32_t level_max8(uint32_t v)
 {
@@ -113,20 +107,20 @@ __global__ __launch_bounds__(kLevelThreads) void k_level(const LevelParams P, co
     wl[tid] = w[tid];
   }
 
-  level_u4 next = {0u, 0u, 0u, 0u};
+  pcm_u4 next = {0u, 0u, 0u, 0u};
   if (tid * kLevelPer < n)
   {
-    next = level_load8(row + tid * kLevelPer);
+    next = pcm_load8(row + tid * kLevelPer);
   }
   for (uint32_t s0 = 0; s0 < n; s0 += kLevelStep)
   {
     // 1. the samples and the frame's peak
     const uint32_t at = s0 + tid * kLevelPer;              // the lane's first sample
     const bool active = at < n;                            // n is whole blocks: a lane has all of its samples or none
-    const level_u4 cur = next;
+    const pcm_u4 cur = next;
     if (at + kLevelStep < n)
     {
-      next = level_load8(row + at + kLevelStep);
+      next = pcm_load8(row + at + kLevelStep);
     }
     const uint32_t d[4] = {cur.x, cur.y, cur.z, cur.w};
     int32_t x[kLevelPer];
@@ -176,12 +170,12 @@ __global__ __launch_bounds__(kLevelThreads) void k_level(const LevelParams P, co
       {
         y[i] = (uint32_t)(bypass ? x[i] : level_output(x[i], level_sample_gain(g_prev, g, sub * kLevelPer + i)));
       }
-      level_u4 v;
+      pcm_u4 v;
       v.x = (y[0] & 0xffffu) | (y[1] << 16);
       v.y = (y[2] & 0xffffu) | (y[3] << 16);
       v.z = (y[4] & 0xffffu) | (y[5] << 16);
       v.w = (y[6] & 0xffffu) | (y[7] << 16);
-      level_store8(orow + at, v);
+      pcm_store8(orow + at, v);
     }
   }
 
@@ -294,15 +288,7 @@ extern "C" int hrfd_level_set_bypass(hrfd_level *l, uint32_t channel, int on)
   return HRFD_OK;
 }
 
-extern "C" int hrfd_level_reset(hrfd_level *l, uint32_t channel)
-{
-  BANK_TRY(hrfd::pcm_check_channel("hrfd_level_reset", channel, 65536));
-  BANK_TRY(hrfd::bank_need_handle("hrfd_level_reset", l));
-  BANK_TRY(hrfd::pcm_check_channel("hrfd_level_reset", channel, l->n_channels));
-  std::lock_guard<std::mutex> g(l->core.mu);
-  l->hist.mark(channel);
-  return HRFD_OK;
-}
+extern "C" int hrfd_level_reset(hrfd_level *l, uint32_t channel) { return hrfd::bank_reset_history(l, "hrfd_level_reset", channel); }
 
 static int level_check_process(hrfd_level *l, const char *who, const void *pcm, uint64_t stride, bool device_entry, const void *n_pcm,
                                uint32_t n_blocks, const void *out, uint64_t out_stride, const void *gain, const void *peak)

@@ -1,6 +1,7 @@
 // hackrfdiags_amd/csrc/hrfd_pcm.h -- the PCM contract of the banks behind the receive chain (hrfd_tone, hrfd_audio,
 // hrfd_resamp, hrfd_level, hrfd_afsk, and hrfd_hdlc behind that) and in front of the transmit chain (hrfd_tonegen, hrfd_afskgen), in one place: rows of int16 at an even address, an even stride apart, in blocks of 512 samples of
-// which an optional n_pcm says how many count; the rounding of a FIR over them; and the argument checks the banks share.
+// which an optional n_pcm says how many count; the rounding of a FIR over them; the argument checks the banks share; and,
+// for the kernels, the access to 8 consecutive samples of a row (pcm_load8, pcm_store8).
 // Plain C++ like hrfd_bank.h (tests/cpp/san_pcm.cc compiles it on the CPU); the includer declares
 // `int fail(int code, const char *fmt, ...)` and the HRFD_* codes first.
 #pragma once
@@ -30,6 +31,15 @@ HRFD_PCM_HD int32_t pcm_sat16(int64_t v) { return (int32_t)(v < -32768 ? -32768 
 // y = sat16((acc + 2^13) >> 14).  Taps with sum |h| <= 65535 (bank_tap_sums_ok) and |x| <= 32768 give |acc| <= 65535 *
 // 32768 = 2^31 - 2^15 < 2^31 - 2^14, so acc + 2^13 stays inside int32 as every partial sum does
 HRFD_PCM_HD int32_t pcm_fir_round(int32_t acc) { return pcm_sat16((int64_t)((acc + (1 << 13)) >> 14)); }
+
+#if defined(__HIPCC__)
+// 8 consecutive samples of a row, the 16 bytes one lane of k_level, k_afsk, k_tonegen and k_afskgen loads and stores: rows at
+// any even address and stride take one path through a vector type of alignment 2
+typedef uint32_t pcm_u4 __attribute__((ext_vector_type(4)));
+typedef uint32_t pcm_u4_any __attribute__((ext_vector_type(4), aligned(2)));
+__device__ __forceinline__ pcm_u4 pcm_load8(const int16_t *src) { return *(const pcm_u4_any *)src; }
+__device__ __forceinline__ void pcm_store8(int16_t *dst, pcm_u4 v) { *(pcm_u4_any *)dst = v; }
+#endif
 
 // ---- the shared checks, each under `who`, the public function's name
 inline int pcm_check_channels(const char *who, uint32_t n_channels, const void *out)

@@ -4,8 +4,9 @@
 //
 // PCM rows [C][n_blocks][512] int16 in (or none: generate only), the same rows with the tones added out, clips per channel
 // and, optionally, which tracks sound in every block.  Exact integer arithmetic on the tone bank's phase grid, contract in
-// include/hrfd.h; tests/tonegen_model.py restates it in numpy, hrfd_tonegen.h holds the laws and the queue rules both sides
-// of this file share.
+// include/hrfd.h; tests/tonegen_model.py restates it in numpy, hrfd_gen.h and hrfd_tonegen.h hold the laws and the queue
+// rules both sides of this file share.  The clock, the clip counters, the sine table and the process entries are GenCore's
+// (hrfd_bank.hip); the queues, their copy on the device and the launch are this file's.
 //
 // The handle keeps the queues on the host (two tracks of at most 32 segments per channel, absolute stream times) and a copy
 // on the device: 64 slots of 32 bytes per channel, the unused ones empty.  The kernel is given the stream time N of the
@@ -27,7 +28,7 @@
 //      behind the last tile, and added to clips[c] with one vector atomic per wave that has any
 //   5. active: wave w of a tile tests the slots against block w of the tile, lane 0 writes the two track bits
 // In place: every sample is loaded once, by the lane that stores it.  Rows at any even address and stride take one path
-// through a vector type of alignment 2, as in hrfd_level.hip.
+// through a vector type of alignment 2 (pcm_load8, pcm_store8).
 // The grid is at most 65536 x 64 = 2^22 workgroups = kBankMaxWgs: the launch is never cut (no first_wg, no max_wgs hook).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,7 +44,7 @@ namespace hrfd {
 constexpr int kTonegenThreads = 256;
 constexpr int kTonegenPer = 8;                             // consecutive samples of one lane: 16 bytes
 constexpr int kTonegenTile = kTonegenThreads * kTonegenPer;      // 2048 samples
-constexpr int kTonegenTileBlocks = kTonegenTile / (int)kTonegenBlock;      // 4: one per wave
+constexpr int kTonegenTileBlocks = kTonegenTile / (int)kGenBlock;  // 4: one per wave
 constexpr uint32_t kTonegenMaxGridY = 64;
 constexpr uint32_t kTonegenAimWgs = 2048;                  // workgroups a launch aims for before a workgroup takes a second tile
 constexpr uint32_t kTonegenStageChannels = 1024;           // channels of one upload from the pinned staging buffer
@@ -51,9 +52,6 @@ constexpr int32_t kTonegenClamp = 1 << 20;                 // |k + 1| and |end -
 static_assert(kTonegenTileBlocks == kTonegenThreads / 64, "one wave per block of a tile");
 static_assert(kTonegenSlots == 64, "one slot per lane of a wave");
 static_assert(65536ull * kTonegenMaxGridY <= kBankMaxWgs, "the grid is one launch");
-
-typedef uint32_t tonegen_u4 __attribute__((ext_vector_type(4)));
-typedef uint32_t tonegen_u4_any __attribute__((ext_vector_type(4), aligned(2)));      // 16 bytes at any even address
 
 struct TonegenParams
 {
@@ -68,9 +66,6 @@ struct TonegenParams
   uint32_t n_blocks;
 };
 
-__device__ __forceinline__ tonegen_u4 tonegen_load8(const int16_t *src) { return *(const tonegen_u4_any *)src; }
-__device__ __forceinline__ void tonegen_store8(int16_t *dst, tonegen_u4 v) { *(tonegen_u4_any *)dst = v; }
-
 __device__ __forceinline__ int32_t tonegen_clamp(int64_t v)
 {
   return (int32_t)(v < -(int64_t)kTonegenClamp ? -(int64_t)kTonegenClamp : (v > (int64_t)kTonegenClamp ? (int64_t)kTonegenClamp : v));
@@ -82,7 +77,7 @@ __global__ __launch_bounds__(kTonegenThreads) void k_tonegen(const TonegenParams
   __shared__ int16_t sl[4096];
   __shared__ TonegenSlot slot[kTonegenSlots];
   const uint32_t tid = threadIdx.x, c = blockIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint32_t n = P.n_blocks * kTonegenBlock;
+  const uint32_t n = P.n_blocks * kGenBlock;
   const int16_t *row = P.pcm != nullptr ? (const int16_t *)((const char *)P.pcm + (uint64_t)c * P.stride) : nullptr;
   int16_t *orow = (int16_t *)((char *)P.out + (uint64_t)c * P.out_stride);
   const bool in_place = (const int16_t *)orow == row;
@@ -94,8 +89,8 @@ __global__ __launch_bounds__(kTonegenThreads) void k_tonegen(const TonegenParams
   if (row_busy)
   {
     // 2. the table and the slots
-    const tonegen_u4 *src = (const tonegen_u4 *)sine;
-    tonegen_u4 *dst = (tonegen_u4 *)sl;
+    const pcm_u4 *src = (const pcm_u4 *)sine;
+    pcm_u4 *dst = (pcm_u4 *)sl;
     dst[tid] = src[tid];
     dst[tid + kTonegenThreads] = src[tid + kTonegenThreads];
     if (tid < kTonegenSlots)
@@ -116,9 +111,9 @@ __global__ __launch_bounds__(kTonegenThreads) void k_tonegen(const TonegenParams
     if (P.active != nullptr)
     {
       // 5. wave w: block w of the tile
-      const uint64_t b0 = n0 + wave * kTonegenBlock;
-      const uint64_t m = row_busy ? __ballot(s_start < b0 + kTonegenBlock && s_end > b0) : 0ull;
-      const uint32_t b = t0 / kTonegenBlock + wave;
+      const uint64_t b0 = n0 + wave * kGenBlock;
+      const uint64_t m = row_busy ? __ballot(s_start < b0 + kGenBlock && s_end > b0) : 0ull;
+      const uint32_t b = t0 / kGenBlock + wave;
       if (lane == 0 && b < P.n_blocks)
       {
         P.active[(uint64_t)c * P.n_blocks + b] = (uint8_t)(((uint32_t)m != 0u ? 1u : 0u) | ((uint32_t)(m >> 32) != 0u ? 2u : 0u));
@@ -128,14 +123,14 @@ __global__ __launch_bounds__(kTonegenThreads) void k_tonegen(const TonegenParams
     {
       continue;                                            // (no barrier in this loop)
     }
-    tonegen_u4 cur = {0u, 0u, 0u, 0u};
+    pcm_u4 cur = {0u, 0u, 0u, 0u};
     if (row != nullptr)
     {
-      cur = tonegen_load8(row + at);
+      cur = pcm_load8(row + at);
     }
     if (hits == 0ull)
     {
-      tonegen_store8(orow + at, cur);                      // a copy, or zeros
+      pcm_store8(orow + at, cur);                          // a copy, or zeros
       continue;
     }
     int32_t sum[kTonegenPer];
@@ -166,8 +161,8 @@ __global__ __launch_bounds__(kTonegenThreads) void k_tonegen(const TonegenParams
         const int32_t up = up0 + i, down = down0 - i;
         if (up >= 1 && down >= 1)
         {
-          const int32_t v = tonegen_mix(amp_a, sl[tonegen_cos_index(th_a)], amp_b, sl[tonegen_cos_index(th_b)]);
-          sum[i] += tonegen_ramp(v, (uint32_t)up, (uint32_t)down);
+          const int32_t v = gen_mix(amp_a, sl[gen_cos_index(th_a)], amp_b, sl[gen_cos_index(th_b)]);
+          sum[i] += gen_ramp(v, (uint32_t)up, (uint32_t)down);
         }
         th_a += s.step_a;
         th_b += s.step_b;
@@ -181,15 +176,15 @@ __global__ __launch_bounds__(kTonegenThreads) void k_tonegen(const TonegenParams
     {
       const int32_t x = (i & 1) ? (int32_t)d[i / 2] >> 16 : (int32_t)(int16_t)d[i / 2];
       bool clip;
-      y[i] = (uint32_t)tonegen_output(x, sum[i], &clip);
+      y[i] = (uint32_t)gen_output(x, sum[i], &clip);
       clipped += clip ? 1u : 0u;
     }
-    tonegen_u4 v;
+    pcm_u4 v;
     v.x = (y[0] & 0xffffu) | (y[1] << 16);
     v.y = (y[2] & 0xffffu) | (y[3] << 16);
     v.z = (y[4] & 0xffffu) | (y[5] << 16);
     v.w = (y[6] & 0xffffu) | (y[7] << 16);
-    tonegen_store8(orow + at, v);
+    pcm_store8(orow + at, v);
   }
 
   if (__ballot(clipped != 0u) != 0ull)
@@ -212,23 +207,15 @@ __global__ __launch_bounds__(kTonegenThreads) void k_tonegen(const TonegenParams
 struct hrfd_tonegen
 {
   hrfd::BankCore core;
+  hrfd::GenCore gen;                       // the clock, the clips, the sine table, the host path's staging
   uint32_t n_channels = 0;
 
   // host records, under core.mu
-  uint64_t N = 0;                          // the stream time of the next call's first sample
   std::vector<hrfd::TonegenTrack> track;   // [C][2]
-  uint64_t next_end = hrfd::kTonegenNoEnd; // no segment ends before this: a call below it has nothing to drop
   uint32_t dirty_lo = 0, dirty_hi = 0;     // channels dirty_lo .. dirty_hi - 1 differ from the device's copy
-  bool clear_clips = false;                // reset: the counters are zeroed ahead of the next launch
 
   hrfd::PinnedBuf<hrfd::TonegenSlot> h_stage;      // [min(C, 1024)][64]
   hrfd::DevBuf<hrfd::TonegenSlot> d_slots; // [C][64]
-  hrfd::DevBuf<int16_t> d_sine;            // [4096]
-  hrfd::DevBuf<unsigned long long> d_clips;        // [C]
-
-  // host-path staging
-  hrfd::DevBuf<int16_t> d_pcm, d_out;
-  hrfd::DevBuf<uint8_t> d_active;
 
   hrfd::TonegenTrack &q(uint32_t c, uint32_t t) { return track[(size_t)c * hrfd::kTonegenTracks + t]; }
 
@@ -259,15 +246,8 @@ extern "C" int hrfd_tonegen_create(uint32_t n_channels, int device, hrfd_tonegen
   t->track.resize(C * kTonegenTracks);
   t->dirty_lo = 0;
   t->dirty_hi = n_channels;                // the device's copy starts as empty slots, through the first call's staging
-  std::vector<int16_t> sine(4096);
-  for (uint32_t i = 0; i < 4096; i++)
-  {
-    sine[i] = Q_DDC_COS[(i - 1024u) & 4095u];
-  }
-  if (!(t->d_slots.alloc(C * kTonegenSlots) && t->d_sine.alloc(4096) && t->d_clips.alloc(C) &&
-        t->h_stage.alloc(std::min<size_t>(C, kTonegenStageChannels) * kTonegenSlots) &&
-        hipMemcpy(t->d_sine, sine.data(), sizeof(int16_t) * 4096, hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemset(t->d_clips, 0, sizeof(unsigned long long) * C) == hipSuccess))
+  if (!(t->d_slots.alloc(C * kTonegenSlots) && t->h_stage.alloc(std::min<size_t>(C, kTonegenStageChannels) * kTonegenSlots) &&
+        t->gen.alloc(C)))
   {
     (void)hipGetLastError();
     bank_free(t);
@@ -293,9 +273,9 @@ extern "C" int hrfd_tonegen_queue(hrfd_tonegen *t, uint32_t channel, uint32_t tr
   const char *who = "hrfd_tonegen_queue";
   BANK_TRY(tonegen_check_segments(who, segs, n, track));
   BANK_TRY(pcm_check_channel(who, channel, 65536));
-  if (start != kTonegenAppend)
+  if (start != kGenAppend)
   {
-    BANK_TRY(tonegen_check_time(who, start));
+    BANK_TRY(gen_check_time(who, start));
   }
   BANK_TRY(bank_need_handle(who, t));
   BANK_TRY(pcm_check_channel(who, channel, t->n_channels));
@@ -305,14 +285,14 @@ extern "C" int hrfd_tonegen_queue(hrfd_tonegen *t, uint32_t channel, uint32_t tr
   std::vector<TonegenTrack> merged(last - first);
   for (uint32_t c = first; c < last; c++)
   {
-    BANK_TRY(tonegen_lay_out(who, t->q(c, track), t->N, segs, n, start, merged[c - first]));
+    BANK_TRY(tonegen_lay_out(who, t->q(c, track), t->gen.N, segs, n, start, merged[c - first]));
   }
   for (uint32_t c = first; c < last; c++)
   {
     t->q(c, track).swap(merged[c - first]);
     for (const TonegenSlot &s : t->q(c, track))
     {
-      t->next_end = std::min(t->next_end, s.end);
+      t->gen.next_end = std::min(t->gen.next_end, s.end);
     }
     t->touch(c);
   }
@@ -330,10 +310,10 @@ extern "C" int hrfd_tonegen_cut(hrfd_tonegen *t, uint32_t channel, uint32_t trac
     TonegenTrack &q = t->q(c, track);
     if (!q.empty())
     {
-      tonegen_cut(q, t->N);
+      tonegen_cut(q, t->gen.N);
       for (const TonegenSlot &s : q)
       {
-        t->next_end = std::min(t->next_end, s.end);
+        t->gen.next_end = std::min(t->gen.next_end, s.end);
       }
       t->touch(c);
     }
@@ -349,34 +329,22 @@ extern "C" int hrfd_tonegen_reset(hrfd_tonegen *t)
   {
     q.clear();
   }
-  t->N = 0;
-  t->next_end = hrfd::kTonegenNoEnd;
+  t->gen.reset();
   t->dirty_lo = 0;
   t->dirty_hi = t->n_channels;
-  t->clear_clips = true;
   return HRFD_OK;
 }
 
 extern "C" int hrfd_tonegen_set_time(hrfd_tonegen *t, uint64_t N)
 {
-  BANK_TRY(hrfd::tonegen_check_time("hrfd_tonegen_set_time", N));
+  BANK_TRY(hrfd::gen_check_time("hrfd_tonegen_set_time", N));
   BANK_TRY(hrfd::bank_need_handle("hrfd_tonegen_set_time", t));
   std::lock_guard<std::mutex> g(t->core.mu);
-  t->N = N;
+  t->gen.N = N;
   return HRFD_OK;
 }
 
-extern "C" int hrfd_tonegen_time(hrfd_tonegen *t, uint64_t *N)
-{
-  if (N == nullptr)
-  {
-    return fail(HRFD_EINVAL, "hrfd_tonegen_time: NULL result");
-  }
-  BANK_TRY(hrfd::bank_need_handle("hrfd_tonegen_time", t));
-  std::lock_guard<std::mutex> g(t->core.mu);
-  *N = t->N;
-  return HRFD_OK;
-}
+extern "C" int hrfd_tonegen_time(hrfd_tonegen *t, uint64_t *N) { return hrfd::gen_time(t, "hrfd_tonegen_time", N); }
 
 extern "C" int hrfd_tonegen_pending(hrfd_tonegen *t, uint32_t channel, uint32_t track, uint32_t *n_segments, uint64_t *end)
 {
@@ -390,18 +358,14 @@ extern "C" int hrfd_tonegen_pending(hrfd_tonegen *t, uint32_t channel, uint32_t 
   {
     return fail(HRFD_EINVAL, "%s: NULL results", who);
   }
-  BANK_TRY(bank_need_handle(who, t));
-  if (channel >= t->n_channels)
-  {
-    return fail(HRFD_EINVAL, "%s: channel %u (0..%u)", who, channel, t->n_channels - 1);
-  }
+  BANK_TRY(gen_check_getter(t, who, channel));
   std::lock_guard<std::mutex> g(t->core.mu);
   // counted without dropping: what has ended leaves the queue with the next call
   uint32_t count = 0;
-  uint64_t last = t->N;
+  uint64_t last = t->gen.N;
   for (const TonegenSlot &s : t->q(channel, track))
   {
-    if (s.end > t->N)
+    if (s.end > t->gen.N)
     {
       count++;
       last = s.end;
@@ -420,42 +384,7 @@ extern "C" int hrfd_tonegen_pending(hrfd_tonegen *t, uint32_t channel, uint32_t 
 
 extern "C" int hrfd_tonegen_get_clips(hrfd_tonegen *t, uint32_t channel, uint64_t *n)
 {
-  using namespace hrfd;
-  const char *who = "hrfd_tonegen_get_clips";
-  if (n == nullptr || channel >= 65536)
-  {
-    return fail(HRFD_EINVAL, "%s: channel %u (one channel) and a result pointer", who, channel);
-  }
-  BANK_TRY(bank_need_handle(who, t));
-  if (channel >= t->n_channels)
-  {
-    return fail(HRFD_EINVAL, "%s: channel %u (0..%u)", who, channel, t->n_channels - 1);
-  }
-  {
-    std::lock_guard<std::mutex> g(t->core.mu);
-    if (t->clear_clips)
-    {
-      *n = 0;                              // reset, and no call since
-      return HRFD_OK;
-    }
-  }
-  HIP_TRY(hipSetDevice(t->core.device));
-  BANK_TRY(t->core.drain());
-  unsigned long long v = 0;
-  HIP_TRY(hipMemcpy(&v, t->d_clips + channel, sizeof(v), hipMemcpyDeviceToHost));
-  *n = v;
-  return HRFD_OK;
-}
-
-static int tonegen_check_process(hrfd_tonegen *t, const char *who, const void *pcm, uint64_t stride, bool device_entry,
-                                 uint32_t n_blocks, const void *out, uint64_t out_stride)
-{
-  // what the sizes and addresses decide on their own comes first, so that it is refused with its own text
-  BANK_TRY(hrfd::tonegen_check_call(who, pcm, stride, device_entry, n_blocks, out, out_stride, 1));
-  BANK_TRY(hrfd::bank_need_handle(who, t));
-  BANK_TRY(hrfd::tonegen_check_call(who, pcm, stride, device_entry, n_blocks, out, out_stride, t->n_channels));
-  std::lock_guard<std::mutex> g(t->core.mu);
-  return hrfd::tonegen_check_time(who, t->N + (uint64_t)hrfd::kTonegenBlock * n_blocks - 1);       // the call's last sample
+  return hrfd::gen_get_clips(t, "hrfd_tonegen_get_clips", channel, n);
 }
 
 // the channels lo .. hi - 1 from the host's queues to the device's slots, through the pinned staging buffer in uploads of
@@ -483,30 +412,30 @@ static int tonegen_launch(hrfd_tonegen *t, const int16_t *d_pcm, uint64_t stride
                           uint64_t out_stride, uint8_t *d_active, hipStream_t st)
 {
   using namespace hrfd;
-  const uint64_t n = (uint64_t)kTonegenBlock * n_blocks;
+  const uint64_t n = (uint64_t)kGenBlock * n_blocks;
   TonegenParams P;
   BANK_TRY(t->core.order_behind_last(st));
   {
     std::lock_guard<std::mutex> g(t->core.mu);
-    P.N = t->N;
-    if (t->next_end <= t->N)
+    P.N = t->gen.N;
+    if (t->gen.next_end <= t->gen.N)
     {
       // segments have ended: they leave the queues, and the device's copy of their channels with them
-      t->next_end = kTonegenNoEnd;
+      t->gen.next_end = kTonegenNoEnd;
       for (uint32_t c = 0; c < t->n_channels; c++)
       {
         for (uint32_t k = 0; k < kTonegenTracks; k++)
         {
           TonegenTrack &q = t->q(c, k);
           const size_t before = q.size();
-          tonegen_drop_ended(q, t->N);
+          tonegen_drop_ended(q, t->gen.N);
           if (q.size() != before)
           {
             t->touch(c);
           }
           for (const TonegenSlot &s : q)
           {
-            t->next_end = std::min(t->next_end, s.end);
+            t->gen.next_end = std::min(t->gen.next_end, s.end);
           }
         }
       }
@@ -516,25 +445,20 @@ static int tonegen_launch(hrfd_tonegen *t, const int16_t *d_pcm, uint64_t stride
       BANK_TRY(tonegen_stage(t, t->dirty_lo, t->dirty_hi, st));
       t->dirty_lo = t->dirty_hi = 0;
     }
-    if (t->clear_clips)
-    {
-      HIP_TRY(hipMemsetAsync(t->d_clips, 0, sizeof(unsigned long long) * t->n_channels, st));
-      t->clear_clips = false;
-    }
-    t->N += n;
+    BANK_TRY(t->gen.advance(t->n_channels, n, st));
   }
   P.pcm = d_pcm;
   P.stride = stride;
   P.out = d_out;
   P.out_stride = out_stride;
   P.slots = t->d_slots;
-  P.clips = t->d_clips;
+  P.clips = t->gen.d_clips;
   P.active = d_active;
   P.n_blocks = n_blocks;
   const uint32_t tiles = (uint32_t)((n + kTonegenTile - 1) / kTonegenTile);
   const uint32_t want = (kTonegenAimWgs + t->n_channels - 1) / t->n_channels;
   const uint32_t gy = std::min(std::min(tiles, kTonegenMaxGridY), std::max(want, 1u));
-  hipLaunchKernelGGL(k_tonegen, dim3(t->n_channels, gy), dim3(kTonegenThreads), 0, st, P, (const int16_t *)t->d_sine.p);
+  hipLaunchKernelGGL(k_tonegen, dim3(t->n_channels, gy), dim3(kTonegenThreads), 0, st, P, (const int16_t *)t->gen.d_sine.p);
   BANK_TRY(bank_launch_ok("k_tonegen"));
   t->core.launched_on(st);
   return HRFD_OK;
@@ -543,24 +467,11 @@ static int tonegen_launch(hrfd_tonegen *t, const int16_t *d_pcm, uint64_t stride
 extern "C" int hrfd_tonegen_process_device(hrfd_tonegen *t, const int16_t *d_pcm, uint64_t channel_stride_bytes, uint32_t n_blocks,
                                            int16_t *d_out, uint64_t out_stride_bytes, uint8_t *d_active, void *stream)
 {
-  BANK_TRY(tonegen_check_process(t, "hrfd_tonegen_process_device", d_pcm, channel_stride_bytes, true, n_blocks, d_out,
-                                 out_stride_bytes));
-  HIP_TRY(hipSetDevice(t->core.device));
-  return tonegen_launch(t, d_pcm, channel_stride_bytes, n_blocks, d_out, out_stride_bytes, d_active, t->core.stream_or_own(stream));
+  return hrfd::gen_process_device(t, "hrfd_tonegen_process_device", tonegen_launch, d_pcm, channel_stride_bytes, n_blocks, d_out,
+                                  out_stride_bytes, d_active, stream);
 }
 
 extern "C" int hrfd_tonegen_process(hrfd_tonegen *t, const int16_t *pcm, uint32_t n_blocks, int16_t *out, uint8_t *active)
 {
-  using namespace hrfd;
-  BANK_TRY(tonegen_check_process(t, "hrfd_tonegen_process", pcm, 0, false, n_blocks, out, 0));
-  BankHostCall call(t->core);
-  const size_t C = t->n_channels, row = 2 * (size_t)kTonegenBlock * n_blocks;
-  const int16_t *d_pcm = call.up(t->d_pcm, pcm, row * C);
-  int16_t *d_out = call.room(t->d_out, out, row * C);
-  uint8_t *d_active = call.room(t->d_active, active, C * n_blocks);
-  BANK_TRY(call.rc);
-  BANK_TRY(tonegen_launch(t, d_pcm, row, n_blocks, d_out, row, d_active, call.st));
-  call.down(out, d_out, row * C);
-  call.down(active, d_active, C * n_blocks);
-  return call.finish();
+  return hrfd::gen_process(t, "hrfd_tonegen_process", tonegen_launch, pcm, n_blocks, out, active);
 }

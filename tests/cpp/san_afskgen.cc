@@ -23,6 +23,7 @@ static int fail(int code, const char *fmt, ...)
   return code;
 }
 #include "../../hackrfdiags_amd/csrc/hrfd_afskgen.h"
+#include "../../hackrfdiags_amd/csrc/hrfd_tonegen.h"         // for the one tone against the tone generator's slow loop
 #include "../../hackrfdiags_amd/csrc/hrfd_ddc_tables.h"
 
 using namespace hrfd;
@@ -57,7 +58,7 @@ static hrfd_afskgen_message msg(uint32_t n_bits, uint32_t baud = kBaud1200, uint
 static int check_the_checks()
 {
   static_assert(kAfskgenMaxMessages == HRFD_AFSKGEN_MAX_MESSAGES && kAfskgenMaxBits == HRFD_AFSKGEN_MAX_BITS &&
-                    kAfskgenMaxBlocks == HRFD_AFSKGEN_MAX_BLOCKS && kAfskgenNrzi == HRFD_AFSKGEN_NRZI && kAfskgenAppend == HRFD_AFSKGEN_APPEND,
+                    kGenMaxBlocks == HRFD_AFSKGEN_MAX_BLOCKS && kAfskgenNrzi == HRFD_AFSKGEN_NRZI && kGenAppend == HRFD_AFSKGEN_APPEND,
                 "the header's limits are the public ones");
   static_assert(sizeof(hrfd_afskgen_message) == 32, "eight uint32");
   int out = 0;
@@ -103,20 +104,20 @@ static int check_the_checks()
   m = msg(8192, 16385);
   CHECK(afskgen_check_message("who", &m, bits.data(), &L) == HRFD_OK && L == 2147352584ull);
 
-  CHECK(afskgen_check_time("who", (1ull << 63) - 1) == HRFD_OK && refused(afskgen_check_time("who", 1ull << 63), "below 2^63"));
+  CHECK(gen_check_time("who", (1ull << 63) - 1) == HRFD_OK && refused(gen_check_time("who", 1ull << 63), "below 2^63"));
   alignas(16) static char buf[65536];
   const void *in = buf + 16384, *far = buf + 40960;
-  CHECK(refused(afskgen_check_call("who", in, 1024, true, 0, far, 1024, 1), "n_blocks"));
-  CHECK(refused(afskgen_check_call("who", in, 1 << 21, true, 1025, far, 1 << 21, 1), "n_blocks"));
-  CHECK(refused(afskgen_check_call("who", in, 1024, true, 1, nullptr, 1024, 1), "NULL argument"));
-  CHECK(refused(afskgen_check_call("who", in, 1022, true, 1, far, 1024, 1), "channel_stride_bytes"));
-  CHECK(refused(afskgen_check_call("who", in, 1024, true, 1, far, 1027, 1), "out_stride_bytes"));
-  CHECK(afskgen_check_call("who", nullptr, 0, true, 1, far, 1024, 7) == HRFD_OK);
-  CHECK(refused(afskgen_check_call("who", buf + 16385, 1024, true, 1, far, 1024, 1), "even addresses"));
-  CHECK(afskgen_check_call("who", in, 1030, true, 1, in, 1030, 4) == HRFD_OK && afskgen_check_call("who", in, 0, false, 3, in, 0, 4) == HRFD_OK);
-  CHECK(refused(afskgen_check_call("who", in, 1030, true, 1, in, 1032, 4), "overlaps"));
-  CHECK(refused(afskgen_check_call("who", in, 1024, true, 1, buf + 16384 + 1024, 1024, 4), "overlaps"));
-  CHECK(afskgen_check_call("who", in, 1024, true, 1, buf + 16384 + 4096, 1024, 4) == HRFD_OK);
+  CHECK(refused(gen_check_call("who", in, 1024, true, 0, far, 1024, 1), "n_blocks"));
+  CHECK(refused(gen_check_call("who", in, 1 << 21, true, 1025, far, 1 << 21, 1), "n_blocks"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, nullptr, 1024, 1), "NULL argument"));
+  CHECK(refused(gen_check_call("who", in, 1022, true, 1, far, 1024, 1), "channel_stride_bytes"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, far, 1027, 1), "out_stride_bytes"));
+  CHECK(gen_check_call("who", nullptr, 0, true, 1, far, 1024, 7) == HRFD_OK);
+  CHECK(refused(gen_check_call("who", buf + 16385, 1024, true, 1, far, 1024, 1), "even addresses"));
+  CHECK(gen_check_call("who", in, 1030, true, 1, in, 1030, 4) == HRFD_OK && gen_check_call("who", in, 0, false, 3, in, 0, 4) == HRFD_OK);
+  CHECK(refused(gen_check_call("who", in, 1030, true, 1, in, 1032, 4), "overlaps"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, buf + 16384 + 1024, 1024, 4), "overlaps"));
+  CHECK(gen_check_call("who", in, 1024, true, 1, buf + 16384 + 4096, 1024, 4) == HRFD_OK);
   return 0;
 }
 
@@ -213,7 +214,7 @@ static int check_queue()
   CHECK(afskgen_check_message("who", &m, bits.data(), &L) == HRFD_OK && L == 21);
   CHECK(afskgen_lay_out("who", q, 0, &m, L, 1000, &s) == HRFD_OK && s.start == 1010 && s.end == 1031 && s.amp == 8000);
   CHECK(afskgen_insert(q, s, std::vector<uint32_t>(1, 7u)) == 0);
-  CHECK(afskgen_lay_out("who", q, 0, &m, L, kAfskgenAppend, &s) == HRFD_OK && s.start == 1041 && s.end == 1062);
+  CHECK(afskgen_lay_out("who", q, 0, &m, L, kGenAppend, &s) == HRFD_OK && s.start == 1041 && s.end == 1062);
   CHECK(afskgen_insert(q, s, std::vector<uint32_t>(1, 7u)) == 1);
   CHECK(afskgen_lay_out("who", q, 0, &m, L, 0, &s) == HRFD_OK && s.start == 10);                 // in front
   CHECK(afskgen_insert(q, s, std::vector<uint32_t>(1, 7u)) == 2 && q[0].s.start == 10 && q[0].slot == 2 && q[1].slot == 0 && q[2].slot == 1);
@@ -230,12 +231,12 @@ static int check_queue()
         end == 1062);
   // the four, and the slot a message that ended leaves
   CHECK(afskgen_lay_out("who", q, 0, &m, L, 2000, &s) == HRFD_OK && afskgen_insert(q, s, std::vector<uint32_t>(1, 7u)) == 3);
-  CHECK(refused(afskgen_lay_out("who", q, 30, &m, L, kAfskgenAppend, &s), "5 messages"));
-  CHECK(afskgen_lay_out("who", q, 31, &m, L, kAfskgenAppend, &s) == HRFD_OK && s.start == 2041);         // the first has ended
+  CHECK(refused(afskgen_lay_out("who", q, 30, &m, L, kGenAppend, &s), "5 messages"));
+  CHECK(afskgen_lay_out("who", q, 31, &m, L, kGenAppend, &s) == HRFD_OK && s.start == 2041);         // the first has ended
   afskgen_drop_ended(q, 31);
   CHECK(q.size() == 3 && afskgen_insert(q, s, std::vector<uint32_t>(1, 7u)) == 2 && q.back().s.start == 2041);
   // append where everything has ended: from N
-  CHECK(afskgen_lay_out("who", q, 5000, &m, L, kAfskgenAppend, &s) == HRFD_OK && s.start == 5010);
+  CHECK(afskgen_lay_out("who", q, 5000, &m, L, kGenAppend, &s) == HRFD_OK && s.start == 5010);
   // times near 2^63
   q.clear();
   CHECK(afskgen_lay_out("who", q, 0, &m, L, (1ull << 63) - 32, &s) == HRFD_OK && s.end == (1ull << 63) - 1);
@@ -291,7 +292,7 @@ static int32_t restated(const AfskgenSlot &s, const uint8_t *level, uint64_t n, 
 
 static int check_slow_loop()
 {
-  const uint32_t B = 9, n = B * kAfskgenBlock;
+  const uint32_t B = 9, n = B * kGenBlock;
   const uint32_t bauds[4] = {kBaud1200, kBaud300, kTop, kOdd};
   for (int round = 0; round < 8; round++)
   {
@@ -315,7 +316,7 @@ static int check_slow_loop()
       uint64_t L = 0;
       AfskgenSlot s;
       CHECK(afskgen_check_message("who", &m, bits.data(), &L) == HRFD_OK);
-      CHECK(afskgen_lay_out("who", q, N, &m, L, j == 0 ? N + next() % 600 : kAfskgenAppend, &s) == HRFD_OK);
+      CHECK(afskgen_lay_out("who", q, N, &m, L, j == 0 ? N + next() % 600 : kGenAppend, &s) == HRFD_OK);
       std::vector<uint32_t> lv((n_bits + 31) / 32);
       afskgen_levels(bits.data(), n_bits, (m.flags & 1) != 0, lv.data());
       std::vector<uint8_t> plain(n_bits);
@@ -372,9 +373,9 @@ static int check_slow_loop()
       uint8_t on = 0;
       for (uint32_t j = 0; j < count; j++)
       {
-        for (uint32_t i = 0; i < kAfskgenBlock && !on; i++)
+        for (uint32_t i = 0; i < kGenBlock && !on; i++)
         {
-          const uint64_t at = N + (uint64_t)b * kAfskgenBlock + i;
+          const uint64_t at = N + (uint64_t)b * kGenBlock + i;
           on = at >= slots[j].start && at < slots[j].end;
         }
       }
@@ -386,16 +387,16 @@ static int check_slow_loop()
     uint64_t clips_c = 0, clips_io = 0;
     for (uint32_t k : cuts)
     {
-      const uint64_t Nk = N + (uint64_t)at * kAfskgenBlock;
-      std::vector<int16_t> in(x.begin() + at * kAfskgenBlock, x.begin() + (at + k) * kAfskgenBlock), out(k * kAfskgenBlock), g(k * kAfskgenBlock);
+      const uint64_t Nk = N + (uint64_t)at * kGenBlock;
+      std::vector<int16_t> in(x.begin() + at * kGenBlock, x.begin() + (at + k) * kGenBlock), out(k * kGenBlock), g(k * kGenBlock);
       std::vector<uint8_t> a(k);
       clips_c += afskgen_channel_slow(in.data(), k, slots, lv, count, Nk, Q_DDC_COS, out.data(), a.data());
-      memcpy(yc.data() + at * kAfskgenBlock, out.data(), 2 * out.size());
+      memcpy(yc.data() + at * kGenBlock, out.data(), 2 * out.size());
       memcpy(actc + at, a.data(), k);
       clips_io += afskgen_channel_slow(in.data(), k, slots, lv, count, Nk, Q_DDC_COS, in.data(), nullptr);
-      memcpy(io.data() + at * kAfskgenBlock, in.data(), 2 * in.size());
+      memcpy(io.data() + at * kGenBlock, in.data(), 2 * in.size());
       afskgen_channel_slow(nullptr, k, slots, lv, count, Nk, Q_DDC_COS, g.data(), nullptr);
-      memcpy(genc.data() + at * kAfskgenBlock, g.data(), 2 * g.size());
+      memcpy(genc.data() + at * kGenBlock, g.data(), 2 * g.size());
       at += k;
     }
     afskgen_channel_slow(nullptr, B, slots, lv, count, N, Q_DDC_COS, gen.data(), actg);

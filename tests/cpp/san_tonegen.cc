@@ -1,4 +1,5 @@
-// Sanitizer harness for the HIP-free part of the tone generator bank (hackrfdiags_amd/csrc/hrfd_tonegen.h), CPU only: compiled
+// Sanitizer harness for the HIP-free part of the tone generator bank (hackrfdiags_amd/csrc/hrfd_tonegen.h, and hrfd_gen.h,
+// which it shares with the AFSK generator), CPU only: compiled
 // as plain C++ under -fsanitize=address,undefined (tests/test_tonegen_sanitizers.py).  Every check at its limit with its text,
 // the laws on their boundaries (the zero crossing at k = 0, both signs of the rounding, the largest mix, the ramp's ends),
 // every rule of the queue (append, insertion, overlap, FOREVER, the 32 segments, times near 2^63), the cut, and the slow loop:
@@ -51,8 +52,8 @@ static hrfd_tonegen_segment seg(uint32_t length, uint32_t step_a = 0, uint32_t a
 static int check_the_checks()
 {
   static_assert(kTonegenTracks == HRFD_TONEGEN_TRACKS && kTonegenMaxSegments == HRFD_TONEGEN_MAX_SEGMENTS &&
-                    kTonegenMaxBlocks == HRFD_TONEGEN_MAX_BLOCKS && kTonegenForever == HRFD_TONEGEN_FOREVER &&
-                    kTonegenAppend == HRFD_TONEGEN_APPEND,
+                    kGenMaxBlocks == HRFD_TONEGEN_MAX_BLOCKS && kTonegenForever == HRFD_TONEGEN_FOREVER &&
+                    kGenAppend == HRFD_TONEGEN_APPEND,
                 "the header's limits are the public ones");
   static_assert(sizeof(hrfd_tonegen_segment) == 24, "six uint32");
   int out = 0;
@@ -84,68 +85,70 @@ static int check_the_checks()
   s33[3] = seg(0xfffffffeu);
   CHECK(tonegen_check_segments("who", s33, 5, 0) == HRFD_OK);
 
-  CHECK(tonegen_check_time("who", 0) == HRFD_OK && tonegen_check_time("who", (1ull << 63) - 1) == HRFD_OK);
-  CHECK(refused(tonegen_check_time("who", 1ull << 63), "below 2^63") && refused(tonegen_check_time("who", ~0ull), "below 2^63"));
+  CHECK(gen_check_time("who", 0) == HRFD_OK && gen_check_time("who", (1ull << 63) - 1) == HRFD_OK);
+  CHECK(refused(gen_check_time("who", 1ull << 63), "below 2^63") && refused(gen_check_time("who", ~0ull), "below 2^63"));
+  CHECK(gen_check_one_channel("who", 0, 1) == HRFD_OK && gen_check_one_channel("who", 65535, 65536) == HRFD_OK);
+  CHECK(refused(gen_check_one_channel("who", 5, 5), "channel 5 (0..4)") && refused(gen_check_one_channel("who", HRFD_ALL_CHANNELS, 65536), "(0..65535)"));
   CHECK(tonegen_check_track("who", 4, 1, 5) == HRFD_OK && tonegen_check_track("who", HRFD_ALL_CHANNELS, 0, 1) == HRFD_OK);
   CHECK(refused(tonegen_check_track("who", 5, 0, 5), "channel 5") && refused(tonegen_check_track("who", 0, 2, 5), "track 2"));
 
   alignas(16) static char buf[65536];
   const void *in = buf + 16384, *far = buf + 40960;
-  CHECK(refused(tonegen_check_call("who", in, 1024, true, 0, far, 1024, 1), "n_blocks"));
-  CHECK(refused(tonegen_check_call("who", in, 1 << 21, true, 1025, far, 1 << 21, 1), "n_blocks"));
-  CHECK(refused(tonegen_check_call("who", in, 1024, true, 1, nullptr, 1024, 1), "NULL argument"));
-  CHECK(refused(tonegen_check_call("who", in, 1022, true, 1, far, 1024, 1), "channel_stride_bytes"));
-  CHECK(refused(tonegen_check_call("who", in, 1025, true, 1, far, 1024, 1), "channel_stride_bytes"));
-  CHECK(refused(tonegen_check_call("who", in, 1024, true, 1, far, 1022, 1), "out_stride_bytes"));
-  CHECK(refused(tonegen_check_call("who", in, 1024, true, 1, far, 1027, 1), "out_stride_bytes"));
-  CHECK(tonegen_check_call("who", nullptr, 0, true, 1, far, 1024, 7) == HRFD_OK);          // generate only: no input stride
-  CHECK(refused(tonegen_check_call("who", nullptr, 0, true, 1, far, 1022, 7), "out_stride_bytes"));
-  CHECK(tonegen_check_call("who", in, 0, false, 1, far, 0, 2) == HRFD_OK);                 // the host entry has no strides
-  CHECK(tonegen_check_call("who", nullptr, 0, false, 1024, far, 0, 1) == HRFD_OK);
-  CHECK(refused(tonegen_check_call("who", buf + 16385, 1024, true, 1, far, 1024, 1), "even addresses"));
-  CHECK(refused(tonegen_check_call("who", in, 1024, true, 1, buf + 40961, 1024, 1), "even addresses"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 0, far, 1024, 1), "n_blocks"));
+  CHECK(refused(gen_check_call("who", in, 1 << 21, true, 1025, far, 1 << 21, 1), "n_blocks"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, nullptr, 1024, 1), "NULL argument"));
+  CHECK(refused(gen_check_call("who", in, 1022, true, 1, far, 1024, 1), "channel_stride_bytes"));
+  CHECK(refused(gen_check_call("who", in, 1025, true, 1, far, 1024, 1), "channel_stride_bytes"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, far, 1022, 1), "out_stride_bytes"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, far, 1027, 1), "out_stride_bytes"));
+  CHECK(gen_check_call("who", nullptr, 0, true, 1, far, 1024, 7) == HRFD_OK);          // generate only: no input stride
+  CHECK(refused(gen_check_call("who", nullptr, 0, true, 1, far, 1022, 7), "out_stride_bytes"));
+  CHECK(gen_check_call("who", in, 0, false, 1, far, 0, 2) == HRFD_OK);                 // the host entry has no strides
+  CHECK(gen_check_call("who", nullptr, 0, false, 1024, far, 0, 1) == HRFD_OK);
+  CHECK(refused(gen_check_call("who", buf + 16385, 1024, true, 1, far, 1024, 1), "even addresses"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, buf + 40961, 1024, 1), "even addresses"));
   // in place: the input's own address and stride, and nothing else that overlaps
-  CHECK(tonegen_check_call("who", in, 1030, true, 1, in, 1030, 4) == HRFD_OK);
-  CHECK(tonegen_check_call("who", in, 0, false, 3, in, 0, 4) == HRFD_OK);
-  CHECK(refused(tonegen_check_call("who", in, 1030, true, 1, in, 1032, 4), "overlaps"));
-  CHECK(refused(tonegen_check_call("who", in, 1030, true, 1, in, 1032, 1), "in place means"));
-  CHECK(refused(tonegen_check_call("who", in, 1024, true, 1, buf + 16386, 1024, 1), "overlaps"));
-  CHECK(refused(tonegen_check_call("who", in, 1024, true, 1, buf + 16384 - 2, 1024, 1), "overlaps"));
-  CHECK(refused(tonegen_check_call("who", in, 1024, true, 1, buf + 16384 + 1022, 1024, 1), "overlaps"));
-  CHECK(tonegen_check_call("who", in, 1024, true, 1, buf + 16384 + 1024, 1024, 1) == HRFD_OK);
-  CHECK(tonegen_check_call("who", in, 1024, true, 1, buf + 16384 - 1024, 1024, 1) == HRFD_OK);
-  CHECK(refused(tonegen_check_call("who", in, 1024, true, 1, buf + 16384 + 1024, 1024, 4), "overlaps"));      // inside the rows of four
-  CHECK(tonegen_check_call("who", in, 1024, true, 1, buf + 16384 + 4096, 1024, 4) == HRFD_OK);
+  CHECK(gen_check_call("who", in, 1030, true, 1, in, 1030, 4) == HRFD_OK);
+  CHECK(gen_check_call("who", in, 0, false, 3, in, 0, 4) == HRFD_OK);
+  CHECK(refused(gen_check_call("who", in, 1030, true, 1, in, 1032, 4), "overlaps"));
+  CHECK(refused(gen_check_call("who", in, 1030, true, 1, in, 1032, 1), "in place means"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, buf + 16386, 1024, 1), "overlaps"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, buf + 16384 - 2, 1024, 1), "overlaps"));
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, buf + 16384 + 1022, 1024, 1), "overlaps"));
+  CHECK(gen_check_call("who", in, 1024, true, 1, buf + 16384 + 1024, 1024, 1) == HRFD_OK);
+  CHECK(gen_check_call("who", in, 1024, true, 1, buf + 16384 - 1024, 1024, 1) == HRFD_OK);
+  CHECK(refused(gen_check_call("who", in, 1024, true, 1, buf + 16384 + 1024, 1024, 4), "overlaps"));      // inside the rows of four
+  CHECK(gen_check_call("who", in, 1024, true, 1, buf + 16384 + 4096, 1024, 4) == HRFD_OK);
   return 0;
 }
 
 static int check_laws()
 {
   // 1. the index: rounded to the nearest of 4096, the sine a quarter turn behind the cosine, zero at theta = 0
-  CHECK(tonegen_cos_index(0) == 0 && tonegen_cos_index((1u << 19) - 1) == 0 && tonegen_cos_index(1u << 19) == 1);
-  CHECK(tonegen_cos_index(0xfff80000u) == 0 && tonegen_cos_index(0xfff7ffffu) == 4095);
-  CHECK(tonegen_sin_index(0) == 3072 && Q_DDC_COS[3072] == 0 && Q_DDC_COS[tonegen_sin_index(1u << 30)] == 32767);
-  CHECK(Q_DDC_COS[tonegen_sin_index(3u << 30)] == -32767 && Q_DDC_COS[tonegen_sin_index(1u << 31)] == 0);
+  CHECK(gen_cos_index(0) == 0 && gen_cos_index((1u << 19) - 1) == 0 && gen_cos_index(1u << 19) == 1);
+  CHECK(gen_cos_index(0xfff80000u) == 0 && gen_cos_index(0xfff7ffffu) == 4095);
+  CHECK(gen_sin_index(0) == 3072 && Q_DDC_COS[3072] == 0 && Q_DDC_COS[gen_sin_index(1u << 30)] == 32767);
+  CHECK(Q_DDC_COS[gen_sin_index(3u << 30)] == -32767 && Q_DDC_COS[gen_sin_index(1u << 31)] == 0);
   // 2. the mix: the largest sums, the rounding on both signs (the shift is arithmetic)
-  CHECK(tonegen_mix(32767, 32767, 32767, 32767) == 65532 && tonegen_mix(32767, -32767, 32767, -32767) == -65532);
-  CHECK(tonegen_mix(1, 16384, 0, 0) == 1 && tonegen_mix(1, 16383, 0, 0) == 0 && tonegen_mix(1, -16384, 0, 0) == 0 &&
-        tonegen_mix(1, -16385, 0, 0) == -1);
-  CHECK(tonegen_mix(0, 32767, 0, -32767) == 0 && tonegen_mix(32767, 32767, 32767, -32767) == 0);
+  CHECK(gen_mix(32767, 32767, 32767, 32767) == 65532 && gen_mix(32767, -32767, 32767, -32767) == -65532);
+  CHECK(gen_mix(1, 16384, 0, 0) == 1 && gen_mix(1, 16383, 0, 0) == 0 && gen_mix(1, -16384, 0, 0) == 0 &&
+        gen_mix(1, -16385, 0, 0) == -1);
+  CHECK(gen_mix(0, 32767, 0, -32767) == 0 && gen_mix(32767, 32767, 32767, -32767) == 0);
   // 3. the ramp: e = 64 gives v itself; the ends; the rounding
   for (int32_t v : {-65534, -1, 0, 1, 77, 65534})
   {
-    CHECK(tonegen_ramp(v, 64, 64) == v && tonegen_ramp(v, 1000, 64) == v && tonegen_ramp(v, 64, 1u << 20) == v);
+    CHECK(gen_ramp(v, 64, 64) == v && gen_ramp(v, 1000, 64) == v && gen_ramp(v, 64, 1u << 20) == v);
   }
-  CHECK(tonegen_ramp(6400, 1, 64) == 100 && tonegen_ramp(6400, 64, 1) == 100 && tonegen_ramp(6400, 63, 2) == 200 &&
-        tonegen_ramp(6400, 32, 33) == 3200);
-  CHECK(tonegen_ramp(1, 32, 64) == 1 && tonegen_ramp(1, 31, 64) == 0 && tonegen_ramp(-1, 32, 64) == 0 && tonegen_ramp(-1, 33, 64) == -1);
-  CHECK(tonegen_ramp(65534, 63, 64) == 64510 && tonegen_ramp(-65534, 64, 63) == -64510);
+  CHECK(gen_ramp(6400, 1, 64) == 100 && gen_ramp(6400, 64, 1) == 100 && gen_ramp(6400, 63, 2) == 200 &&
+        gen_ramp(6400, 32, 33) == 3200);
+  CHECK(gen_ramp(1, 32, 64) == 1 && gen_ramp(1, 31, 64) == 0 && gen_ramp(-1, 32, 64) == 0 && gen_ramp(-1, 33, 64) == -1);
+  CHECK(gen_ramp(65534, 63, 64) == 64510 && gen_ramp(-65534, 64, 63) == -64510);
   // 4. the output
   bool clip;
-  CHECK(tonegen_output(32767, 0, &clip) == 32767 && !clip && tonegen_output(32767, 1, &clip) == 32767 && clip);
-  CHECK(tonegen_output(-32768, 0, &clip) == -32768 && !clip && tonegen_output(-32768, -1, &clip) == -32768 && clip);
-  CHECK(tonegen_output(-32768, 131068, &clip) == 32767 && clip && tonegen_output(32767, -131068, &clip) == -32768 && clip);
-  CHECK(tonegen_output(-32768, 65535, &clip) == 32767 && !clip && tonegen_output(100, -200, &clip) == -100 && !clip);
+  CHECK(gen_output(32767, 0, &clip) == 32767 && !clip && gen_output(32767, 1, &clip) == 32767 && clip);
+  CHECK(gen_output(-32768, 0, &clip) == -32768 && !clip && gen_output(-32768, -1, &clip) == -32768 && clip);
+  CHECK(gen_output(-32768, 131068, &clip) == 32767 && clip && gen_output(32767, -131068, &clip) == -32768 && clip);
+  CHECK(gen_output(-32768, 65535, &clip) == 32767 && !clip && gen_output(100, -200, &clip) == -100 && !clip);
   return 0;
 }
 
@@ -168,16 +171,16 @@ static int check_queue()
     CHECK(refused(tonegen_lay_out("who", q, 0, &one, 1, start, m), "overlap"));
   }
   CHECK(tonegen_lay_out("who", q, 0, &one, 1, 1160, m) == HRFD_OK);
-  CHECK(tonegen_lay_out("who", q, 0, &one, 1, kTonegenAppend, m) == HRFD_OK && m.back().start == 1160 && m.back().end == 1162);
-  CHECK(tonegen_lay_out("who", q, 5000, &one, 1, kTonegenAppend, m) == HRFD_OK && m.size() == 1 && m[0].start == 5000);       // all ended
+  CHECK(tonegen_lay_out("who", q, 0, &one, 1, kGenAppend, m) == HRFD_OK && m.back().start == 1160 && m.back().end == 1162);
+  CHECK(tonegen_lay_out("who", q, 5000, &one, 1, kGenAppend, m) == HRFD_OK && m.size() == 1 && m[0].start == 5000);       // all ended
   CHECK(refused(tonegen_lay_out("who", q, 1050, &one, 1, 1049, m), "before the stream time 1050"));
   CHECK(tonegen_lay_out("who", q, 1050, &one, 1, 1160, m) == HRFD_OK && m.size() == 4 && m[0].start == 1000);    // [0, 1000) has ended
   one = seg(kTonegenForever, 5, 6, 7, 8, 3);
-  CHECK(tonegen_lay_out("who", q, 0, &one, 1, kTonegenAppend, m) == HRFD_OK && m.back().start == 1163 && m.back().end == kTonegenNoEnd);
+  CHECK(tonegen_lay_out("who", q, 0, &one, 1, kGenAppend, m) == HRFD_OK && m.back().start == 1163 && m.back().end == kTonegenNoEnd);
   CHECK(m.back().step_a == 5 && m.back().step_b == 7 && m.back().amps == (6u | (8u << 16)));
   q = m;
   one = seg(1);
-  CHECK(refused(tonegen_lay_out("who", q, 0, &one, 1, kTonegenAppend, m), "appended behind a FOREVER"));
+  CHECK(refused(tonegen_lay_out("who", q, 0, &one, 1, kGenAppend, m), "appended behind a FOREVER"));
   CHECK(refused(tonegen_lay_out("who", q, 0, &one, 1, 1ull << 40, m), "behind the FOREVER segment at 1163"));
   CHECK(tonegen_lay_out("who", q, 0, &one, 1, 1160, m) == HRFD_OK);                        // in front of it still
   CHECK(tonegen_track_end(q) == kTonegenNoEnd);
@@ -188,11 +191,11 @@ static int check_queue()
   {
     s = seg(1);
   }
-  CHECK(tonegen_lay_out("who", q, 0, many, 32, kTonegenAppend, m) == HRFD_OK && m.size() == 32 && m[31].end == 32);
+  CHECK(tonegen_lay_out("who", q, 0, many, 32, kGenAppend, m) == HRFD_OK && m.size() == 32 && m[31].end == 32);
   q = m;
-  CHECK(refused(tonegen_lay_out("who", q, 0, many, 1, kTonegenAppend, m), "33 segments"));
-  CHECK(refused(tonegen_lay_out("who", q, 31, many, 32, kTonegenAppend, m), "33 segments"));          // one has not ended
-  CHECK(tonegen_lay_out("who", q, 32, many, 32, kTonegenAppend, m) == HRFD_OK && m.size() == 32 && m[0].start == 32);
+  CHECK(refused(tonegen_lay_out("who", q, 0, many, 1, kGenAppend, m), "33 segments"));
+  CHECK(refused(tonegen_lay_out("who", q, 31, many, 32, kGenAppend, m), "33 segments"));          // one has not ended
+  CHECK(tonegen_lay_out("who", q, 32, many, 32, kGenAppend, m) == HRFD_OK && m.size() == 32 && m[0].start == 32);
   // times near 2^63
   q.clear();
   one = seg(0xfffffffeu, 0, 0, 0, 0, 0xffffffffu);
@@ -255,7 +258,7 @@ static int32_t restated(const TonegenSlot &s, uint64_t n)
 
 static int check_slow_loop()
 {
-  const uint32_t B = 9, n = B * kTonegenBlock;
+  const uint32_t B = 9, n = B * kGenBlock;
   for (int round = 0; round < 12; round++)
   {
     const uint64_t bases[] = {0, 1, (1ull << 32) - 1024, (1ull << 32) + 5, (1ull << 40) + 333, 1ull << 62};
@@ -313,9 +316,9 @@ static int check_slow_loop()
       uint8_t bits = 0;
       for (uint32_t j = 0; j < kTonegenSlots; j++)
       {
-        for (uint32_t i = 0; i < kTonegenBlock && !(bits >> (j / 32) & 1); i++)
+        for (uint32_t i = 0; i < kGenBlock && !(bits >> (j / 32) & 1); i++)
         {
-          const uint64_t at = N + (uint64_t)b * kTonegenBlock + i;
+          const uint64_t at = N + (uint64_t)b * kGenBlock + i;
           bits |= (uint8_t)((at >= slots[j].start && at < slots[j].end ? 1 : 0) << (j / 32));
         }
       }
@@ -328,11 +331,11 @@ static int check_slow_loop()
     uint64_t clips_c = 0, clips_io = 0;
     for (uint32_t k : cuts)
     {
-      const uint64_t Nk = N + (uint64_t)at * kTonegenBlock;
-      clips_c += tonegen_channel_slow(x.data() + at * kTonegenBlock, k, slots, Nk, Q_DDC_COS, yc.data() + at * kTonegenBlock, actc + at);
-      int16_t *p = io.data() + at * kTonegenBlock;
+      const uint64_t Nk = N + (uint64_t)at * kGenBlock;
+      clips_c += tonegen_channel_slow(x.data() + at * kGenBlock, k, slots, Nk, Q_DDC_COS, yc.data() + at * kGenBlock, actc + at);
+      int16_t *p = io.data() + at * kGenBlock;
       clips_io += tonegen_channel_slow(p, k, slots, Nk, Q_DDC_COS, p, nullptr);
-      tonegen_channel_slow(nullptr, k, slots, Nk, Q_DDC_COS, genc.data() + at * kTonegenBlock, nullptr);
+      tonegen_channel_slow(nullptr, k, slots, Nk, Q_DDC_COS, genc.data() + at * kGenBlock, nullptr);
       at += k;
     }
     tonegen_channel_slow(nullptr, B, slots, N, Q_DDC_COS, gen.data(), actg);
