@@ -193,6 +193,13 @@ def load() -> C.CDLL:
         L.hrfd_duc_process.argtypes = [_vp, _vp, C.c_uint32, _vp]
         L.hrfd_duc_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp]
         L.hrfd_duc_transmit.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp]
+    if hasattr(L, "hrfd_duc_set_key_block"):               # (an older build named by HRFD_LIB has no transmit key)
+        L.hrfd_duc_set_key_block.argtypes = [_vp, C.c_uint32]
+        L.hrfd_duc_n_keys.argtypes = [_vp, C.c_uint32, _u32p]
+        L.hrfd_duc_get_key_skips.argtypes = [_vp, C.POINTER(C.c_uint64)]
+        L.hrfd_duc_process_keyed.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp]
+        L.hrfd_duc_process_device_keyed.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, _vp]
+        L.hrfd_duc_transmit_keyed.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, _vp]
     if hasattr(L, "hrfd_spec_create"):                     # (an older build named by HRFD_LIB has no spectrum bank)
         _u64p = C.POINTER(C.c_uint64)
         L.hrfd_spec_create.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]

@@ -683,24 +683,101 @@ class Duc(_TunedBank):
         check(self.L.hrfd_duc_get_clips(self.h, int(capture), C.byref(v)), "hrfd_duc_get_clips")
         return int(v.value)
 
-    def process(self, channels: np.ndarray, in_bytes: int) -> np.ndarray:
-        """channels int8 [n_channels, in_bytes] -> int8 [n_captures, interpolation * in_bytes]; blocking"""
+    def set_key_block(self, log2_samples: int):
+        """the transmit key's block: 2^log2_samples channel samples per key byte, 10..17 (default 17: one block of 512 PCM
+        samples); from the next call on"""
+        self._call("set_key_block", int(log2_samples))
+
+    def n_keys(self, in_bytes: int) -> int:
+        """key bytes per channel of a call of in_bytes: ceil(in_bytes / 2 / 2^key block)"""
+        v = C.c_uint32(0)
+        self._call("n_keys", int(in_bytes), C.byref(v))
+        return int(v.value)
+
+    def key_skips(self) -> int:
+        """units (channel, tile of 1024 channel samples) the keyed calls skipped since create / reset; waits for the last
+        call"""
+        v = C.c_uint64(0)
+        self._call("get_key_skips", C.byref(v))
+        return int(v.value)
+
+    def process(self, channels: np.ndarray, in_bytes: int, key=None) -> np.ndarray:
+        """channels int8 [n_channels, in_bytes] -> int8 [n_captures, interpolation * in_bytes]; blocking.  key: uint8
+        [n_channels, n_keys(in_bytes)], a channel sends where its byte is non-zero (None: every channel sends)"""
         x = np.ascontiguousarray(channels, dtype=np.int8).reshape(self.n, int(in_bytes))
         out = np.zeros((self.W, self.R * int(in_bytes)), dtype=np.int8)
-        check(self.L.hrfd_duc_process(self.h, _ptr(x), int(in_bytes), _ptr(out)), "hrfd_duc_process")
+        if key is None:
+            check(self.L.hrfd_duc_process(self.h, _ptr(x), int(in_bytes), _ptr(out)), "hrfd_duc_process")
+            return out
+        k = np.ascontiguousarray(key, dtype=np.uint8).reshape(self.n, self.n_keys(in_bytes))
+        self._call("process_keyed", _ptr(x), int(in_bytes), _ptr(k), _ptr(out))
         return out
 
     def process_device(self, d_channels, channel_stride: int, in_bytes: int, d_captures, capture_stride: int,
-                       stream=None):
-        """device pointers (ints); asynchronous on stream (None = the handle's own)"""
-        check(self.L.hrfd_duc_process_device(self.h, _ptr(d_channels), int(channel_stride), int(in_bytes),
-                                             _ptr(d_captures), int(capture_stride), _ptr(stream)),
-              "hrfd_duc_process_device")
+                       stream=None, d_key=None, key_stride: int = 0):
+        """device pointers (ints); asynchronous on stream (None = the handle's own).  d_key: the key rows, key_stride >=
+        n_keys(in_bytes) bytes apart (None: every channel sends)"""
+        if d_key is None:
+            check(self.L.hrfd_duc_process_device(self.h, _ptr(d_channels), int(channel_stride), int(in_bytes),
+                                                 _ptr(d_captures), int(capture_stride), _ptr(stream)),
+                  "hrfd_duc_process_device")
+            return
+        self._call("process_device_keyed", _ptr(d_channels), int(channel_stride), int(in_bytes), _ptr(d_key), int(key_stride),
+                   _ptr(d_captures), int(capture_stride), _ptr(stream))
 
-    def transmit(self, mod: "Mod", d_pcm, n_per_channel: int, d_captures, capture_stride: int, stream=None):
-        """mod's bank over d_pcm, then the DUC over its output (device pointers); asynchronous on stream"""
-        check(self.L.hrfd_duc_transmit(self.h, mod.h, _ptr(d_pcm), int(n_per_channel), _ptr(d_captures),
-                                       int(capture_stride), _ptr(stream)), "hrfd_duc_transmit")
+    def transmit(self, mod: "Mod", d_pcm, n_per_channel: int, d_captures, capture_stride: int, stream=None, d_key=None,
+                 key_stride: int = 0):
+        """mod's bank over d_pcm, then the DUC over its output (device pointers); asynchronous on stream.  d_key as in
+        process_device: the modulator runs over every channel, the DUC over those that are keyed on"""
+        if d_key is None:
+            check(self.L.hrfd_duc_transmit(self.h, mod.h, _ptr(d_pcm), int(n_per_channel), _ptr(d_captures),
+                                           int(capture_stride), _ptr(stream)), "hrfd_duc_transmit")
+            return
+        self._call("transmit_keyed", mod.h, _ptr(d_pcm), int(n_per_channel), _ptr(d_key), int(key_stride), _ptr(d_captures),
+                   int(capture_stride), _ptr(stream))
+
+
+class TxKey:
+    """The transmitters' key from what asks a channel to send: key[c][b] is 1 iff any input is on in one of the stream
+    blocks b - hold .. b of channel c (a block is 64 ms: 512 PCM samples, Duc's default key block).  The inputs are the
+    `active` arrays of ToneGen and AfskGen and a caller's push-to-talk array, torch uint8 tensors [n_channels, n_blocks] on
+    one device, any of them None.  Blocks in front of the first call are off.  hold keeps a channel keyed behind its last
+    on block: the modulator's interpolator and the DUC's channel filter delay a message's tail past the block in which its
+    `active` byte ends ("Keying the transmitters").  The carry between calls is a [n_channels] tensor on
+    the inputs' device, so no call waits for the device."""
+
+    _NEVER = -(1 << 40)
+
+    def __init__(self, n_channels: int, hold: int = 1):
+        if int(n_channels) < 1 or int(hold) < 0:
+            raise ValueError(f"TxKey: n_channels {n_channels} >= 1 and hold {hold} >= 0")
+        self.n, self.hold = int(n_channels), int(hold)
+        self._last = None                                  # [n]: the last on block, counted from the next call's first (< 0)
+
+    def reset(self):
+        self._last = None
+
+    def __call__(self, *inputs):
+        """inputs: uint8 [n_channels, n_blocks] tensors or None (at least one tensor) -> uint8 [n_channels, n_blocks]"""
+        import torch
+        on = None
+        for a in inputs:
+            if a is not None:
+                b = a.reshape(self.n, -1) != 0
+                on = b if on is None else on | b
+        if on is None:
+            raise ValueError("TxKey: at least one input must be a tensor")
+        n = on.shape[1]
+        if n == 0:
+            return torch.zeros((self.n, 0), dtype=torch.uint8, device=on.device)
+        if self._last is None or self._last.device != on.device:
+            self._last = torch.full((self.n,), self._NEVER, dtype=torch.int64, device=on.device)
+        at = torch.arange(n, dtype=torch.int64, device=on.device)
+        # the last on block at or in front of every block, call-local (the carry's are negative)
+        here = torch.where(on, at, torch.full_like(at, self._NEVER))
+        last = torch.maximum(torch.cummax(here, dim=1).values, self._last[:, None])
+        self._last = torch.clamp(last[:, -1] - n, min=self._NEVER)
+        return ((at - last) <= self.hold).to(torch.uint8).contiguous()
 
 SPEC_MAX_FRAMES = 65536
 SPEC_MAX_THRESHOLD = 1 << 44

@@ -16,12 +16,18 @@
 // After the last channel: one rounded, saturated int8 store per output and one clip count per workgroup (a wave
 // reduction, an LDS counter, one global atomicAdd).  C extra workgroups per launch copy the last H samples of every
 // channel into the other history buffer (ping-pong: the tiles of the same launch read the current one).
+//
+// The transmit key (k_duc<R, true>; hrfd_duc_key.h): a key byte per (channel, block of 2^k samples).  A
+// keyed-off sample is read as zero, by the history workgroups as well, and a unit (channel, tile) whose own key block and
+// the one in front of it are off is skipped ahead of every load: zeros through every stage are zeros.  The decision is
+// uniform over the workgroup, which counts its skipped units and adds them to the handle's meter once.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
 #include <vector>
 
+#include "hrfd_duc_key.h"
 #include "hrfd_duc_tables.h"
 
 namespace hrfd {
@@ -63,6 +69,11 @@ struct DucParams
   int TA, TB;                  // 0 = bypass
   int LA;                      // stage A look-back in channel samples: (TA - 1) / R
   int JA, JB;                  // packed tap dwords in use (JA per branch)
+  // the transmit key (k_duc<R, true> only)
+  const uint8_t *key;          // [C] rows of ceil(M / 2^key_log2) bytes, key_stride apart
+  uint64_t key_stride;
+  uint32_t key_log2;
+  unsigned long long *skips;   // the units skipped since create / reset
 };
 
 // one IQ sample of channel c at call-local index j (history in front of the call, zeros beyond it) as (I, Q) bytes
@@ -100,7 +111,7 @@ __device__ __forceinline__ uint32_t duc_load_pair(const DucParams &P, uint32_t c
 
 __device__ __forceinline__ uint32_t pack16(int lo, int hi) { return ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16); }
 
-template <int R>
+template <int R, bool KEYED>
 __global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
 {
   __shared__ uint32_t cs[4096];
@@ -108,6 +119,7 @@ __global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
   __shared__ uint32_t vI[kDucVDw], vQ[kDucVDw];
   __shared__ uint2 taps[kDucJA + kDucJB];
   __shared__ uint32_t clip_sum;
+  __shared__ uint32_t skip_sum;                         // keyed: this workgroup's skipped units, thread 0's alone
   const int tid = threadIdx.x;
   const uint32_t n_units = P.n_tiles * P.n_captures;
   if (blockIdx.x >= n_units)
@@ -116,7 +128,12 @@ __global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
     const uint32_t c = blockIdx.x - n_units;
     for (int i = tid; i < kDucH; i += kDucThreads)
     {
-      const uint32_t v = duc_load_sample(P, c, (int64_t)P.M - kDucH + i);
+      const int64_t j = (int64_t)P.M - kDucH + i;
+      uint32_t v = 0u;
+      if (!KEYED || duc_key_on(P.key + (uint64_t)c * P.key_stride, j, P.M, P.key_log2))
+      {
+        v = duc_load_sample(P, c, j);
+      }
       *(uint16_t *)(P.hist_out + ((uint64_t)c * kDucH + i) * 2) = (uint16_t)v;
     }
     return;
@@ -136,6 +153,10 @@ __global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
   if (tid == 0)
   {
     clip_sum = 0u;
+    if (KEYED)
+    {
+      skip_sum = 0u;
+    }
   }
   const int TA = P.TA, TB = P.TB, LA = P.LA;
   const int LB = TB > 0 ? TB - 1 : 0;
@@ -160,6 +181,28 @@ __global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
   for (uint32_t ci = P.list_off[w]; ci < c_end; ci++)
   {
     const uint32_t c = P.list[ci];
+    // keyed: the u dwords [p_lo, p_hi) are read, the others are zeros.  The look-back lies in the tile in front and so in
+    // one key block, the tile in another or the same; tile 0 looks back into the history, which holds masked samples
+    // already.  The rails' last 16 samples lie behind the tile, where the row may end: no output of the tile needs them
+    // (their stage B outputs meet stage A's zero taps only), so the keyed kernel reads neither them nor their key
+    int p_lo = 0, p_hi = nud;
+    if (KEYED)
+    {
+      const uint8_t *row = P.key + (uint64_t)c * P.key_stride;
+      const uint32_t t = (uint32_t)m_t / kDucTile;
+      if (duc_key_skip(row, t, P.key_log2))
+      {
+        if (tid == 0)
+        {
+          skip_sum++;
+        }
+        continue;                                         // uniform over the workgroup, ahead of the amplitude's mute
+      }
+      const bool on_prev = t == 0u || row[duc_key_block_of((uint32_t)m_t - kDucTile, P.key_log2)] != 0;
+      const bool on_cur = row[duc_key_block_of((uint32_t)m_t, P.key_log2)] != 0;
+      p_lo = on_prev ? 0 : OFF / 2;
+      p_hi = on_cur ? (OFF + kDucTile) / 2 : OFF / 2;
+    }
     const BankTuning ch = P.chan[c];
     if (ch.word == 0u)
     {
@@ -168,7 +211,12 @@ __global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
     // 1. u rails: dword p holds samples m_t - OFF + 2p, + 1 (x << 8 in every half)
     for (int p = tid; p < nud; p += kDucThreads)
     {
-      const uint32_t d = duc_load_pair(P, c, (int64_t)m_t - OFF + 2 * p);
+      uint32_t d = 0u;
+      // both samples of a dword lie in one tile (OFF and the tile are even), so in one key block
+      if (!KEYED || (p >= p_lo && p < p_hi))
+      {
+        d = duc_load_pair(P, c, (int64_t)m_t - OFF + 2 * p);
+      }
       uI[p] = (d & 0x00ff00ffu) << 8;
       uQ[p] = d & 0xff00ff00u;
     }
@@ -344,12 +392,20 @@ __global__ __launch_bounds__(kDucThreads) void k_duc(const DucParams P)
   {
     atomicAdd(P.clips + w, (unsigned long long)clip_sum);
   }
+  if (KEYED && tid == 0 && skip_sum != 0u)
+  {
+    atomicAdd(P.skips, (unsigned long long)skip_sum);
+  }
 }
 
-template __global__ void k_duc<1>(const DucParams);
-template __global__ void k_duc<2>(const DucParams);
-template __global__ void k_duc<4>(const DucParams);
-template __global__ void k_duc<8>(const DucParams);
+template __global__ void k_duc<1, false>(const DucParams);
+template __global__ void k_duc<2, false>(const DucParams);
+template __global__ void k_duc<4, false>(const DucParams);
+template __global__ void k_duc<8, false>(const DucParams);
+template __global__ void k_duc<1, true>(const DucParams);
+template __global__ void k_duc<2, true>(const DucParams);
+template __global__ void k_duc<4, true>(const DucParams);
+template __global__ void k_duc<8, true>(const DucParams);
 
 } // namespace hrfd
 
@@ -369,8 +425,11 @@ struct hrfd_duc
   std::vector<int16_t> tapsA, tapsB;
   bool dirty = true;
   uint64_t N = 0;                          // absolute wideband output-sample counter
-  bool clear_history = true;               // also clears the clip counters
+  bool clear_history = true;               // also clears the clip counters and the count of skipped units
+  uint32_t key_log2 = hrfd::kDucKeyDefaultLog2;   // the key block of the next keyed call
 
+  hrfd::DevBuf<unsigned long long> d_skips;       // [1] units the keyed kernel skipped
+  hrfd::DevBuf<uint8_t> d_key;                    // host-path staging of the key rows
   hrfd::DevBuf<hrfd::BankTuning> d_chan;
   hrfd::DevBuf<uint32_t> d_u32;
   hrfd::DevBuf<uint2> d_taps;
@@ -420,7 +479,7 @@ extern "C" int hrfd_duc_create(uint32_t n_captures, uint32_t n_channels, uint32_
   const size_t n_u32 = 2 * (size_t)n_captures + 1 + n_channels;
   const size_t n_taps = kDucJA + kDucJB;
   const bool ok = d->d_chan.alloc(n_channels) && d->d_u32.alloc(n_u32) && d->d_taps.alloc(n_taps) &&
-                  bank_upload_cos(d->d_cs) && d->d_clips.alloc(n_captures) && d->d_hist[0].alloc(hist_bytes) &&
+                  bank_upload_cos(d->d_cs) && d->d_clips.alloc(n_captures) && d->d_skips.alloc(1) && d->d_hist[0].alloc(hist_bytes) &&
                   d->d_hist[1].alloc(hist_bytes) && d->h_stage_chan.alloc(n_channels) && d->h_stage_u32.alloc(n_u32) &&
                   d->h_stage_taps.alloc(n_taps);
   if (!ok)
@@ -530,9 +589,55 @@ extern "C" int hrfd_duc_get_clips(hrfd_duc *d, uint32_t capture, uint64_t *n)
   return HRFD_OK;
 }
 
-// one launch over every capture on `s`: R * in_bytes per capture from in_bytes per channel
+extern "C" int hrfd_duc_set_key_block(hrfd_duc *d, uint32_t log2_samples)
+{
+  BANK_TRY(hrfd::duc_key_check_block("hrfd_duc_set_key_block", log2_samples));
+  BANK_TRY(hrfd::bank_need_handle("hrfd_duc_set_key_block", d));
+  std::lock_guard<std::mutex> g(d->core.mu);
+  d->key_log2 = log2_samples;              // a launch takes its own copy: the history is untouched
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_n_keys(hrfd_duc *d, uint32_t in_bytes, uint32_t *n)
+{
+  BANK_TRY(hrfd::duc_key_check_result("hrfd_duc_n_keys", n));
+  BANK_TRY(hrfd::bank_need_handle("hrfd_duc_n_keys", d));
+  std::lock_guard<std::mutex> g(d->core.mu);
+  *n = hrfd::duc_key_n(in_bytes / 2u, d->key_log2);
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_duc_get_key_skips(hrfd_duc *d, uint64_t *n)
+{
+  BANK_TRY(hrfd::duc_key_check_result("hrfd_duc_get_key_skips", n));
+  BANK_TRY(hrfd::bank_need_handle("hrfd_duc_get_key_skips", d));
+  HIP_TRY(hipSetDevice(d->core.device));
+  {
+    std::lock_guard<std::mutex> g(d->core.mu);
+    if (d->clear_history)
+    {
+      *n = 0;                              // no launch since create or reset
+      return HRFD_OK;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(d->core.last_stream));
+  unsigned long long v = 0;
+  HIP_TRY(hipMemcpy(&v, d->d_skips, sizeof(v), hipMemcpyDeviceToHost));
+  *n = (uint64_t)v;
+  return HRFD_OK;
+}
+
+// the key block of a call that starts now: a setter on another thread lands before or behind it
+static uint32_t duc_key_log2(hrfd_duc *d)
+{
+  std::lock_guard<std::mutex> g(d->core.mu);
+  return d->key_log2;
+}
+
+// one launch over every capture on `s`: R * in_bytes per capture from in_bytes per channel; d_key NULL: the unkeyed kernel
 static int duc_launch(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_stride, uint32_t in_bytes, int8_t *d_captures,
-                      uint64_t capture_stride, hipStream_t s)
+                      uint64_t capture_stride, hipStream_t s, const uint8_t *d_key = nullptr, uint64_t key_stride = 0,
+                      uint32_t key_log2 = hrfd::kDucKeyDefaultLog2)
 {
   using namespace hrfd;
   BANK_TRY(d->core.order_behind_last(s));
@@ -568,6 +673,7 @@ static int duc_launch(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_st
       {
         HIP_TRY(hipMemsetAsync(d->d_hist[d->cur], 0, (size_t)C * kDucH * 2, s));
         HIP_TRY(hipMemsetAsync(d->d_clips, 0, sizeof(unsigned long long) * W, s));
+        HIP_TRY(hipMemsetAsync(d->d_skips, 0, sizeof(unsigned long long), s));
         d->clear_history = false;
       }
       d->dirty = false;
@@ -592,13 +698,30 @@ static int duc_launch(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_st
   P.n_tiles = (P.M + kDucTile - 1) / kDucTile;
   P.n_channels = C;
   P.n_captures = W;
+  P.key = d_key;
+  P.key_stride = key_stride;
+  P.key_log2 = key_log2;
+  P.skips = d->d_skips;
   const dim3 grid(P.n_tiles * W + C);
-  switch (d->R)
+  if (d_key == nullptr)
   {
-  case 1: hipLaunchKernelGGL(k_duc<1>, grid, dim3(kDucThreads), 0, s, P); break;
-  case 2: hipLaunchKernelGGL(k_duc<2>, grid, dim3(kDucThreads), 0, s, P); break;
-  case 4: hipLaunchKernelGGL(k_duc<4>, grid, dim3(kDucThreads), 0, s, P); break;
-  default: hipLaunchKernelGGL(k_duc<8>, grid, dim3(kDucThreads), 0, s, P); break;
+    switch (d->R)
+    {
+    case 1: hipLaunchKernelGGL((k_duc<1, false>), grid, dim3(kDucThreads), 0, s, P); break;
+    case 2: hipLaunchKernelGGL((k_duc<2, false>), grid, dim3(kDucThreads), 0, s, P); break;
+    case 4: hipLaunchKernelGGL((k_duc<4, false>), grid, dim3(kDucThreads), 0, s, P); break;
+    default: hipLaunchKernelGGL((k_duc<8, false>), grid, dim3(kDucThreads), 0, s, P); break;
+    }
+  }
+  else
+  {
+    switch (d->R)
+    {
+    case 1: hipLaunchKernelGGL((k_duc<1, true>), grid, dim3(kDucThreads), 0, s, P); break;
+    case 2: hipLaunchKernelGGL((k_duc<2, true>), grid, dim3(kDucThreads), 0, s, P); break;
+    case 4: hipLaunchKernelGGL((k_duc<4, true>), grid, dim3(kDucThreads), 0, s, P); break;
+    default: hipLaunchKernelGGL((k_duc<8, true>), grid, dim3(kDucThreads), 0, s, P); break;
+    }
   }
   const int rc = bank_launch_ok("k_duc");
   if (rc != HRFD_OK)
@@ -624,44 +747,62 @@ static int duc_check_call(hrfd_duc *d, const void *channels, uint64_t channel_st
                                d->n_channels);
 }
 
-extern "C" int hrfd_duc_process_device(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_stride, uint32_t in_bytes,
-                                       int8_t *d_captures, uint64_t capture_stride, void *stream)
+// The three entries, with and without a key (key NULL: the unkeyed call), under `who`.  The key's stride is checked against
+// the largest key block first, which needs no handle, then against the handle's; *k is the block the launch uses
+static int duc_check_keyed(hrfd_duc *d, const void *channels, uint64_t channel_stride, uint32_t in_bytes, const void *captures,
+                           uint64_t capture_stride, const void *key, uint64_t key_stride, const char *who, uint32_t *k)
 {
-  BANK_TRY(duc_check_call(d, d_channels, channel_stride, in_bytes, d_captures, capture_stride, "hrfd_duc_process_device"));
-  HIP_TRY(hipSetDevice(d->core.device));
-  return duc_launch(d, d_channels, channel_stride, in_bytes, d_captures, capture_stride, d->core.stream_or_own(stream));
+  BANK_TRY(hrfd::duc_key_check_stride(who, key, key_stride, in_bytes, hrfd::kDucKeyMaxLog2));
+  BANK_TRY(duc_check_call(d, channels, channel_stride, in_bytes, captures, capture_stride, who));
+  *k = duc_key_log2(d);
+  return hrfd::duc_key_check_stride(who, key, key_stride, in_bytes, *k);
 }
 
-extern "C" int hrfd_duc_process(hrfd_duc *d, const int8_t *channels, uint32_t in_bytes, int8_t *captures)
+static int duc_process_device(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_stride, uint32_t in_bytes,
+                              const uint8_t *d_key, uint64_t key_stride, int8_t *d_captures, uint64_t capture_stride, void *stream,
+                              const char *who)
 {
-  BANK_TRY(duc_check_call(d, channels, in_bytes, in_bytes, captures, d ? (uint64_t)d->R * in_bytes : 0, "hrfd_duc_process"));
+  uint32_t k = 0;
+  BANK_TRY(duc_check_keyed(d, d_channels, channel_stride, in_bytes, d_captures, capture_stride, d_key, key_stride, who, &k));
+  HIP_TRY(hipSetDevice(d->core.device));
+  return duc_launch(d, d_channels, channel_stride, in_bytes, d_captures, capture_stride, d->core.stream_or_own(stream), d_key,
+                    key_stride, k);
+}
+
+static int duc_process(hrfd_duc *d, const int8_t *channels, uint32_t in_bytes, const uint8_t *key, int8_t *captures, const char *who)
+{
+  uint32_t k = 0;
+  // the host entry's key is dense: rows of n_keys bytes
+  BANK_TRY(duc_check_keyed(d, channels, in_bytes, in_bytes, captures, d ? (uint64_t)d->R * in_bytes : 0, nullptr, 0, who, &k));
+  const uint32_t n_keys = hrfd::duc_key_n(in_bytes / 2u, k);
   hrfd::BankHostCall call(d->core);
   const size_t in_total = (size_t)d->n_channels * in_bytes, out_total = (size_t)d->n_captures * d->R * in_bytes;
   const int8_t *d_in = call.up(d->d_in, channels, in_total);
+  const uint8_t *d_key = call.up(d->d_key, key, (size_t)d->n_channels * n_keys);
   int8_t *d_out = call.room(d->d_out, captures, out_total);
   BANK_TRY(call.rc);
-  BANK_TRY(duc_launch(d, d_in, in_bytes, in_bytes, d_out, (uint64_t)d->R * in_bytes, call.st));
+  BANK_TRY(duc_launch(d, d_in, in_bytes, in_bytes, d_out, (uint64_t)d->R * in_bytes, call.st, d_key, n_keys, k));
   call.down(captures, d_out, out_total);
   return call.finish();
 }
 
-extern "C" int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pcm, uint32_t n_per_channel,
-                                 int8_t *d_captures, uint64_t capture_stride, void *stream)
+static int duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pcm, uint32_t n_per_channel, const uint8_t *d_key,
+                        uint64_t key_stride, int8_t *d_captures, uint64_t capture_stride, void *stream, const char *who)
 {
   if (mod == nullptr || d_pcm == nullptr || n_per_channel == 0 || n_per_channel > (1u << 16))
   {
-    return fail(HRFD_EINVAL, "hrfd_duc_transmit: NULL argument, or n_per_channel not in 1..65536 (got %u)", n_per_channel);
+    return fail(HRFD_EINVAL, "%s: NULL argument, or n_per_channel not in 1..65536 (got %u)", who, n_per_channel);
   }
   if (d != nullptr && mod->n_channels != d->n_channels)
   {
-    return fail(HRFD_EINVAL, "hrfd_duc_transmit: the modulator has %u channels, the DUC %u", mod->n_channels, d->n_channels);
+    return fail(HRFD_EINVAL, "%s: the modulator has %u channels, the DUC %u", who, mod->n_channels, d->n_channels);
   }
   const uint32_t in_bytes = 512u * n_per_channel;
-  BANK_TRY(duc_check_call(d, d_pcm, in_bytes, in_bytes, d_captures, capture_stride, "hrfd_duc_transmit"));
+  uint32_t k = 0;
+  BANK_TRY(duc_check_keyed(d, d_pcm, in_bytes, in_bytes, d_captures, capture_stride, d_key, key_stride, who, &k));
   if (mod->core.device != d->core.device)
   {
-    return fail(HRFD_EINVAL, "hrfd_duc_transmit: the modulator lives on device %d, the DUC on %d", mod->core.device,
-                d->core.device);
+    return fail(HRFD_EINVAL, "%s: the modulator lives on device %d, the DUC on %d", who, mod->core.device, d->core.device);
   }
   HIP_TRY(hipSetDevice(d->core.device));
   hipStream_t s = d->core.stream_or_own(stream);
@@ -671,8 +812,49 @@ extern "C" int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pc
     HIP_TRY(hipStreamSynchronize(d->core.last_stream));  // the last launch may still read the old buffer
     BANK_TRY(d->d_tx.grow_bytes(need));
   }
-  // the modulator overwrites the buffer the handle's last launch reads: behind it on the device
+  // the modulator overwrites the buffer the handle's last launch reads: behind it on the device.  It runs over every
+  // channel, keyed or not: its state (FM phase, interpolator history) moves on under the key
   BANK_TRY(d->core.order_behind_last(s));
   BANK_TRY(hrfd_mod_process_device(mod, d_pcm, n_per_channel, d->d_tx, s));
-  return duc_launch(d, d->d_tx, in_bytes, in_bytes, d_captures, capture_stride, s);
+  return duc_launch(d, d->d_tx, in_bytes, in_bytes, d_captures, capture_stride, s, d_key, key_stride, k);
 }
+
+extern "C" int hrfd_duc_process_device(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_stride, uint32_t in_bytes,
+                                       int8_t *d_captures, uint64_t capture_stride, void *stream)
+{
+  return duc_process_device(d, d_channels, channel_stride, in_bytes, nullptr, 0, d_captures, capture_stride, stream,
+                            "hrfd_duc_process_device");
+}
+
+extern "C" int hrfd_duc_process_device_keyed(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_stride, uint32_t in_bytes,
+                                             const uint8_t *d_key, uint64_t key_stride, int8_t *d_captures,
+                                             uint64_t capture_stride, void *stream)
+{
+  return duc_process_device(d, d_channels, channel_stride, in_bytes, d_key, key_stride, d_captures, capture_stride, stream,
+                            "hrfd_duc_process_device_keyed");
+}
+
+extern "C" int hrfd_duc_process(hrfd_duc *d, const int8_t *channels, uint32_t in_bytes, int8_t *captures)
+{
+  return duc_process(d, channels, in_bytes, nullptr, captures, "hrfd_duc_process");
+}
+
+extern "C" int hrfd_duc_process_keyed(hrfd_duc *d, const int8_t *channels, uint32_t in_bytes, const uint8_t *key, int8_t *captures)
+{
+  return duc_process(d, channels, in_bytes, key, captures, "hrfd_duc_process_keyed");
+}
+
+extern "C" int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pcm, uint32_t n_per_channel,
+                                 int8_t *d_captures, uint64_t capture_stride, void *stream)
+{
+  return duc_transmit(d, mod, d_pcm, n_per_channel, nullptr, 0, d_captures, capture_stride, stream, "hrfd_duc_transmit");
+}
+
+extern "C" int hrfd_duc_transmit_keyed(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pcm, uint32_t n_per_channel,
+                                       const uint8_t *d_key, uint64_t key_stride, int8_t *d_captures, uint64_t capture_stride,
+                                       void *stream)
+{
+  return duc_transmit(d, mod, d_pcm, n_per_channel, d_key, key_stride, d_captures, capture_stride, stream,
+                      "hrfd_duc_transmit_keyed");
+}
+

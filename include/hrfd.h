@@ -467,11 +467,37 @@ int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captures, uint64_
  *                             [C][512 * n_per_channel], then the DUC over it, both on `stream`: outputs exactly those of
  *                             hrfd_mod_process_device followed by hrfd_duc_process_device; asynchronous
  *   hrfd_duc_get_clips        waits for the handle's last launch, then reads the capture's clip counter
+ *
+ * The transmit key (push-to-talk).  The *_keyed calls take, besides the channel streams, a key row per channel: uint8
+ * [C][n_keys], rows key_stride bytes apart, n_keys = ceil(M / 2^k) for the M = in_bytes / 2 channel samples of the call.  k
+ * is the handle's key block, 10..17 (hrfd_duc_set_key_block; default 17: 131072 channel samples = 262144 bytes = one block
+ * of 512 PCM samples, the granularity of the `active` bytes hrfd_tonegen_* and hrfd_afskgen_* write).  Key byte j of a row
+ * covers the call-local channel samples [j 2^k, (j + 1) 2^k); any non-zero byte is "on":
+ *   xk[c][m] = key[c][m >> k] != 0 ? x[c][m] : 0          (0 <= m < M, call-local)
+ * Everything a keyed call leaves behind is exactly what the unkeyed call leaves behind for the input xk: the captures,
+ * the clip counters, the H = 318 samples of history for the next call (xk, not x) and N.  An all-zero input is exactly zero
+ * at every stage (u = b = v = a = 0, y = (0 + 2^14) >> 15 = 0), so a channel that is keyed off adds nothing to its capture.
+ * A NULL key is the unkeyed call.  The bytes of x inside a keyed-off block are not looked at, and the key is read for
+ * 0 <= m < M only.  Keying is abrupt, there is no ramp: stage B, the channel filter, confines the splatter of the step to
+ * the channel's own +-220 kHz.
+ *   work      the kernel owns one (capture, tile of 1024 channel samples) per workgroup and loops over the capture's
+ *             channels; tiles are call-local, so a tile lies in one key block.  The unit (channel c, tile t) is skipped, with
+ *             none of its loads and none of its arithmetic, iff t >= 1 and key[c][(1024 t) >> k] == 0 and
+ *             key[c][(1024 (t - 1)) >> k] == 0 (the tile's look-back lies in the tile in front of it).  The key is tested in
+ *             front of the amplitude.  Tile 0 of a call looks back into the history and is always computed.
+ *   hrfd_duc_set_key_block    log2 of the key block in channel samples, 10..17; from the next call on, the history stays
+ *   hrfd_duc_n_keys           n_keys of a call of in_bytes under the handle's key block
+ *   hrfd_duc_get_key_skips    waits for the handle's last launch, then reads the units skipped since create / reset (uint64):
+ *                             the idle share of the bank's work
+ *   hrfd_duc_process_keyed    hrfd_duc_process with key [C][n_keys], dense
+ *   hrfd_duc_process_device_keyed   hrfd_duc_process_device with d_key, rows key_stride >= n_keys apart at any address
+ *   hrfd_duc_transmit_keyed   hrfd_duc_transmit with d_key: the modulator bank runs over every channel as in
+ *                             hrfd_duc_transmit (its state moves on whether a channel is keyed or not), then the keyed DUC
  */
 typedef struct hrfd_duc hrfd_duc;
 int hrfd_duc_create(uint32_t n_captures, uint32_t n_channels, uint32_t interpolation, int device, hrfd_duc **out);
 int hrfd_duc_destroy(hrfd_duc *d);
-int hrfd_duc_reset(hrfd_duc *d);              /* history 0, N = 0, every theta_ref = N_ref = 0, clip counters 0 */
+int hrfd_duc_reset(hrfd_duc *d);              /* history 0, N = 0, every theta_ref = N_ref = 0, clip and skip counters 0 */
 int hrfd_duc_set_tuning(hrfd_duc *d, uint32_t channel, uint32_t capture, uint32_t step);
 int hrfd_duc_set_amplitude(hrfd_duc *d, uint32_t channel, uint32_t amplitude);    /* HRFD_ALL_CHANNELS allowed */
 int hrfd_duc_set_output_shift(hrfd_duc *d, uint32_t capture, uint32_t s);         /* HRFD_ALL_CHANNELS: every capture */
@@ -483,6 +509,15 @@ int hrfd_duc_process_device(hrfd_duc *d, const int8_t *d_channels, uint64_t chan
                             int8_t *d_captures, uint64_t capture_stride, void *stream);
 int hrfd_duc_transmit(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pcm, uint32_t n_per_channel, int8_t *d_captures,
                       uint64_t capture_stride, void *stream);
+int hrfd_duc_set_key_block(hrfd_duc *d, uint32_t log2_samples);                  /* 10..17, default 17 */
+int hrfd_duc_n_keys(hrfd_duc *d, uint32_t in_bytes, uint32_t *n);
+int hrfd_duc_get_key_skips(hrfd_duc *d, uint64_t *n);
+int hrfd_duc_process_keyed(hrfd_duc *d, const int8_t *channels, uint32_t in_bytes, const uint8_t *key, int8_t *captures);
+int hrfd_duc_process_device_keyed(hrfd_duc *d, const int8_t *d_channels, uint64_t channel_stride, uint32_t in_bytes,
+                                  const uint8_t *d_key, uint64_t key_stride, int8_t *d_captures, uint64_t capture_stride,
+                                  void *stream);
+int hrfd_duc_transmit_keyed(hrfd_duc *d, hrfd_mod *mod, const int16_t *d_pcm, uint32_t n_per_channel, const uint8_t *d_key,
+                            uint64_t key_stride, int8_t *d_captures, uint64_t capture_stride, void *stream);
 
 /* ------------------------------------------------------------------------------
  * Spectrum bank: W wideband captures -> the power of every FFT bin, and the occupancy of K bands (no reference counterpart
