@@ -180,6 +180,16 @@ def load() -> C.CDLL:
     L.hrfd_ddc_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp]
     L.hrfd_ddc_receive.argtypes = [_vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
                                    _u32p]
+    if hasattr(L, "hrfd_ddc_set_key_block"):               # (an older build named by HRFD_LIB has no receive key)
+        _u64p_key = C.POINTER(C.c_uint64)
+        L.hrfd_ddc_set_key_block.argtypes = [_vp, C.c_uint32]
+        L.hrfd_ddc_n_keys.argtypes = [_vp, C.c_uint32, _u32p]
+        L.hrfd_ddc_get_key_skips.argtypes = [_vp, C.c_uint32, _u64p_key]
+        L.hrfd_ddc_count_key_skips.argtypes = [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _u64p_key, _u64p_key]
+        L.hrfd_ddc_process_keyed.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp]
+        L.hrfd_ddc_process_device_keyed.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, _vp]
+        L.hrfd_ddc_receive_keyed.argtypes = [_vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32,
+                                             _vp, _vp, _vp, _vp, _u32p]
     if hasattr(L, "hrfd_duc_create"):                      # (an older build named by HRFD_LIB has no DUC bank)
         L.hrfd_duc_create.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]
         L.hrfd_duc_destroy.argtypes = [_vp]

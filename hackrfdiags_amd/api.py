@@ -622,26 +622,119 @@ class Ddc(_TunedBank):
         """stage 0 = A (decimating), 1 = B (channel); empty taps = bypass"""
         self._set_filter(stage, taps)
 
-    def process(self, captures: np.ndarray, out_bytes: int) -> np.ndarray:
-        """captures int8 [n_captures, decimation * out_bytes] -> int8 [n_channels, out_bytes]; blocking"""
+    def set_key_block(self, log2_samples: int):
+        """the receive key's block: 2^log2_samples output samples per key byte, 10..17 (default 17: one rx block of 512 PCM
+        samples); from the next call on"""
+        self._call("set_key_block", int(log2_samples))
+
+    def n_keys(self, out_bytes: int) -> int:
+        """key bytes per channel of a call of out_bytes: ceil(out_bytes / 2 / 2^key block)"""
+        v = C.c_uint32(0)
+        self._call("n_keys", int(out_bytes), C.byref(v))
+        return int(v.value)
+
+    def key_skips(self, channel=ALL) -> int:
+        """units (channel, tile of 1024 outputs) the keyed calls skipped since create / reset, of one channel or of the
+        whole bank (ALL); waits for the last call"""
+        v = C.c_uint64(0)
+        self._call("get_key_skips", int(channel), C.byref(v))
+        return int(v.value)
+
+    def process(self, captures: np.ndarray, out_bytes: int, key=None) -> np.ndarray:
+        """captures int8 [n_captures, decimation * out_bytes] -> int8 [n_channels, out_bytes]; blocking.  key: uint8
+        [n_channels, n_keys(out_bytes)], a channel is received where its byte is non-zero and is zeros elsewhere (None:
+        every channel is received)"""
         cap = np.ascontiguousarray(captures, dtype=np.int8).reshape(self.W, self.R * int(out_bytes))
         out = np.zeros((self.n, int(out_bytes)), dtype=np.int8)
-        check(self.L.hrfd_ddc_process(self.h, _ptr(cap), int(out_bytes), _ptr(out)), "hrfd_ddc_process")
+        if key is None:
+            check(self.L.hrfd_ddc_process(self.h, _ptr(cap), int(out_bytes), _ptr(out)), "hrfd_ddc_process")
+            return out
+        k = np.ascontiguousarray(key, dtype=np.uint8).reshape(self.n, self.n_keys(out_bytes))
+        self._call("process_keyed", _ptr(cap), int(out_bytes), _ptr(k), _ptr(out))
         return out
 
-    def process_device(self, d_captures, capture_stride: int, out_bytes: int, d_out, out_stride: int, stream=None):
-        """device pointers (ints); asynchronous on stream (None = the handle's own)"""
-        check(self.L.hrfd_ddc_process_device(self.h, _ptr(d_captures), int(capture_stride), int(out_bytes),
-                                             _ptr(d_out), int(out_stride), _ptr(stream)), "hrfd_ddc_process_device")
+    def process_device(self, d_captures, capture_stride: int, out_bytes: int, d_out, out_stride: int, stream=None,
+                       d_key=None, key_stride: int = 0):
+        """device pointers (ints); asynchronous on stream (None = the handle's own).  d_key: the key rows, key_stride >=
+        n_keys(out_bytes) bytes apart (None: every channel is received)"""
+        if d_key is None:
+            check(self.L.hrfd_ddc_process_device(self.h, _ptr(d_captures), int(capture_stride), int(out_bytes),
+                                                 _ptr(d_out), int(out_stride), _ptr(stream)), "hrfd_ddc_process_device")
+            return
+        self._call("process_device_keyed", _ptr(d_captures), int(capture_stride), int(out_bytes), _ptr(d_key), int(key_stride),
+                   _ptr(d_out), int(out_stride), _ptr(stream))
 
     def receive(self, rx: "Rx", d_captures, capture_stride: int, block_bytes: int, n_blocks: int, d_pcm, d_n_pcm,
-                d_magnitude=None, d_allowed=None) -> int:
-        """the DDC, then rx's bank over its output (device pointers); returns the channels replayed exactly"""
+                d_magnitude=None, d_allowed=None, d_key=None, key_stride: int = 0) -> int:
+        """the DDC, then rx's bank over its output (device pointers); returns the channels replayed exactly.  d_key as in
+        process_device: the DDC runs where a channel is keyed on, rx's bank over every channel"""
         n = C.c_uint32(0)
-        check(self.L.hrfd_ddc_receive(self.h, rx.h, _ptr(d_captures), int(capture_stride), int(block_bytes),
-                                      int(n_blocks), rx.gain_db, _ptr(d_pcm), _ptr(d_n_pcm), _ptr(d_magnitude),
-                                      _ptr(d_allowed), C.byref(n)), "hrfd_ddc_receive")
+        if d_key is None:
+            check(self.L.hrfd_ddc_receive(self.h, rx.h, _ptr(d_captures), int(capture_stride), int(block_bytes),
+                                          int(n_blocks), rx.gain_db, _ptr(d_pcm), _ptr(d_n_pcm), _ptr(d_magnitude),
+                                          _ptr(d_allowed), C.byref(n)), "hrfd_ddc_receive")
+            return int(n.value)
+        self._call("receive_keyed", rx.h, _ptr(d_captures), int(capture_stride), int(block_bytes), int(n_blocks), _ptr(d_key),
+                   int(key_stride), rx.gain_db, _ptr(d_pcm), _ptr(d_n_pcm), _ptr(d_magnitude), _ptr(d_allowed), C.byref(n))
         return int(n.value)
+
+
+def ddc_count_key_skips(key, out_bytes: int, log2_samples: int):
+    """what one keyed call of out_bytes adds to Ddc.key_skips under key block 2^log2_samples, counted on the host unit by
+    unit (hrfd_ddc_count_key_skips): key uint8 [n_channels, n_keys] -> (per channel uint64 [n_channels], their sum)"""
+    k = np.ascontiguousarray(key, dtype=np.uint8)
+    per, total = np.zeros(k.shape[0], dtype=np.uint64), C.c_uint64(0)
+    check(_lib.load().hrfd_ddc_count_key_skips(_ptr(k), k.shape[1], k.shape[0], int(out_bytes), int(log2_samples),
+                                               per.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)),
+          "hrfd_ddc_count_key_skips")
+    return per, int(total.value)
+
+
+class RxKey:
+    """The receivers' key from the spectrum bank's verdicts: key[c][b] is 1 iff channel c's band was present in one of the
+    stream blocks b - hold .. b, or the channel has no band (band_of_channel[c] < 0: always on).  A block is 64 ms: one rx
+    block, Ddc's default key block, one Spectrum call per block.  `present` is Spectrum's uint8 verdict per band, a torch
+    tensor [n_blocks, K] ([K]: one block); any non-zero byte counts.  Blocks in front of the first call are off.  hold keeps
+    a channel open behind its band's last present block: the DDC's filters delay a transmission's tail past the block in
+    which the spectrum last sees it ("Listening only where someone transmits").  The carry between calls is
+    a [n_channels] tensor on the input's device, so no call waits for the device."""
+
+    _NEVER = -(1 << 40)
+
+    def __init__(self, n_channels: int, band_of_channel, hold: int = 1):
+        band = np.asarray(band_of_channel, dtype=np.int64).reshape(-1)
+        if int(n_channels) < 1 or int(hold) < 0 or band.size != int(n_channels):
+            raise ValueError(f"RxKey: n_channels {n_channels} >= 1, hold {hold} >= 0 and one band per channel (got {band.size})")
+        self.n, self.hold = int(n_channels), int(hold)
+        self._band = band
+        self._on_dev = None                                # (band index clamped to 0, always-on mask) on the input's device
+        self._last = None                                  # [n]: the last present block, counted from the next call's first (< 0)
+
+    def reset(self):
+        self._last = None
+
+    def __call__(self, present):
+        """present: uint8 [n_blocks, K] or [K] -> uint8 [n_channels, n_blocks]"""
+        import torch
+        p = present.reshape(1, -1) if present.dim() == 1 else present
+        n, K = int(p.shape[0]), int(p.shape[1])
+        if int(self._band.max()) >= K:
+            raise ValueError(f"RxKey: band {int(self._band.max())} of a channel is not below the spectrum's {K} bands")
+        if n == 0:
+            return torch.zeros((self.n, 0), dtype=torch.uint8, device=p.device)
+        if self._on_dev is None or self._on_dev[0].device != p.device:
+            band = torch.from_numpy(self._band).to(p.device)
+            self._on_dev = (torch.clamp(band, min=0), band < 0)
+        if self._last is None or self._last.device != p.device:
+            self._last = torch.full((self.n,), self._NEVER, dtype=torch.int64, device=p.device)
+        index, always = self._on_dev
+        on = (p.index_select(1, index) != 0).t() | always[:, None]     # [n_channels, n_blocks]
+        at = torch.arange(n, dtype=torch.int64, device=p.device)
+        # the last present block at or in front of every block, call-local (the carry's are negative)
+        here = torch.where(on, at, torch.full_like(at, self._NEVER))
+        last = torch.maximum(torch.cummax(here, dim=1).values, self._last[:, None])
+        self._last = torch.clamp(last[:, -1] - n, min=self._NEVER)
+        return ((at - last) <= self.hold).to(torch.uint8).contiguous()
 
 
 def duc_step(offset_hz: float, interpolation: int) -> int:

@@ -14,12 +14,18 @@
 // odd sample uses the taps shifted by one (a leading zero), so every read is a whole dword.  Taps sit in LDS as
 // (even, odd) pairs and are read as broadcasts.  W extra workgroups per launch copy the last H input samples of every
 // capture into the other history buffer (ping-pong: the tiles of the same launch read the current one).
+//
+// The receive key (k_ddc<R, true>; hrfd_ddc_key.h): a key byte per (channel, block of 2^k outputs).  A
+// workgroup owns one (channel, tile) and nothing of a channel is carried through time, so a unit whose key block is off
+// stores its zeros, counts itself on its channel's meter and returns, ahead of every table, capture and history load.  The
+// history workgroups know no key.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
 #include <vector>
 
+#include "hrfd_ddc_key.h"
 #include "hrfd_ddc_tables.h"
 
 namespace hrfd {
@@ -69,6 +75,11 @@ struct DdcParams
   uint32_t H;
   int TA, TB;                  // 0 = bypass
   int JA, JB;                  // packed tap dwords in use
+  // the receive key (k_ddc<R, true> only)
+  const uint8_t *key;          // [C] rows of ceil(M / 2^key_log2) bytes, key_stride apart
+  uint64_t key_stride;
+  uint32_t key_log2;
+  unsigned long long *skips;   // [C] the units of every channel skipped since create / reset
 };
 
 __device__ __forceinline__ int sat16(int v) { return min(max(v, -32768), 32767); }
@@ -147,7 +158,27 @@ __device__ __forceinline__ uint32_t ddc_load_sample(const DdcParams &P, uint32_t
   return 0u;                               // never under a non-zero tap (the halo is rounded up to whole dwords)
 }
 
-template <int R>
+// n zero bytes at dst, any address: whole 16-byte stores over the aligned middle, bytes at the two ends, nothing past n
+__device__ __forceinline__ void ddc_store_zeros(int8_t *dst, int n, int tid)
+{
+  const int head = min((int)(-(uintptr_t)dst & 15u), n);
+  const int n16 = (n - head) >> 4;
+  const int tail = n - head - 16 * n16;
+  for (int i = tid; i < n16; i += kDdcThreads)
+  {
+    *(uint4 *)(dst + head + 16 * i) = make_uint4(0u, 0u, 0u, 0u);
+  }
+  if (tid < head)
+  {
+    dst[tid] = 0;
+  }
+  if (tid < tail)
+  {
+    dst[head + 16 * n16 + tid] = 0;
+  }
+}
+
+template <int R, bool KEYED>
 __global__ __launch_bounds__(kDdcThreads) void k_ddc(const DdcParams P)
 {
   using L = DdcLds<R>;
@@ -172,6 +203,19 @@ __global__ __launch_bounds__(kDdcThreads) void k_ddc(const DdcParams P)
   const uint32_t c = blockIdx.x / P.n_tiles;
   const int m_t = (int)(blockIdx.x - c * P.n_tiles) * kDdcTile;
   const int cnt = min(kDdcTile, (int)P.M - m_t);
+  if constexpr (KEYED)
+  {
+    // one byte, the same for the whole workgroup, ahead of the tables and their barrier
+    if (ddc_key_skip(P.key + (uint64_t)c * P.key_stride, (uint32_t)m_t / kDdcTile, P.key_log2))
+    {
+      ddc_store_zeros(P.out + (uint64_t)c * P.out_stride + 2 * (uint64_t)m_t, 2 * cnt, tid);
+      if (tid == 0)
+      {
+        atomicAdd(P.skips + c, 1ull);
+      }
+      return;
+    }
+  }
   const BankTuning ch = P.chan[c];
 
   for (int i = tid; i < 4096; i += kDdcThreads)
@@ -380,10 +424,14 @@ __global__ __launch_bounds__(kDdcThreads) void k_ddc(const DdcParams P)
   }
 }
 
-template __global__ void k_ddc<1>(const DdcParams);
-template __global__ void k_ddc<2>(const DdcParams);
-template __global__ void k_ddc<4>(const DdcParams);
-template __global__ void k_ddc<8>(const DdcParams);
+template __global__ void k_ddc<1, false>(const DdcParams);
+template __global__ void k_ddc<2, false>(const DdcParams);
+template __global__ void k_ddc<4, false>(const DdcParams);
+template __global__ void k_ddc<8, false>(const DdcParams);
+template __global__ void k_ddc<1, true>(const DdcParams);
+template __global__ void k_ddc<2, true>(const DdcParams);
+template __global__ void k_ddc<4, true>(const DdcParams);
+template __global__ void k_ddc<8, true>(const DdcParams);
 
 } // namespace hrfd
 
@@ -401,8 +449,11 @@ struct hrfd_ddc
   std::vector<int16_t> tapsA, tapsB;
   bool dirty = true;
   uint64_t N = 0;                          // absolute input-sample counter
-  bool clear_history = true;
+  bool clear_history = true;               // also clears the skip meters
+  uint32_t key_log2 = hrfd::kDdcKeyDefaultLog2;   // the key block of the next keyed call
 
+  hrfd::DevBuf<unsigned long long> d_skips;       // [C] units the keyed kernel skipped, per channel
+  hrfd::DevBuf<uint8_t> d_key;                    // host-path staging of the key rows
   hrfd::DevBuf<hrfd::BankTuning> d_chan;
   hrfd::DevBuf<uint2> d_taps;
   hrfd::DevBuf<uint32_t> d_cs;
@@ -438,7 +489,7 @@ extern "C" int hrfd_ddc_create(uint32_t n_captures, uint32_t n_channels, uint32_
   d->tapsB.assign(Q_DDC_B, Q_DDC_B + N_DDC_B);
   const size_t hist_bytes = (size_t)n_captures * d->H * 2;
   const bool ok = d->d_chan.alloc(n_channels) && d->d_taps.alloc(kDdcJA + kDdcJB) && bank_upload_cos(d->d_cs) &&
-                  d->d_hist[0].alloc(hist_bytes) && d->d_hist[1].alloc(hist_bytes) && d->h_stage_chan.alloc(n_channels) &&
+                  d->d_skips.alloc(n_channels) && d->d_hist[0].alloc(hist_bytes) && d->d_hist[1].alloc(hist_bytes) && d->h_stage_chan.alloc(n_channels) &&
                   d->h_stage_taps.alloc(kDdcJA + kDdcJB);
   if (!ok)
   {
@@ -495,9 +546,77 @@ extern "C" int hrfd_ddc_get_phase(hrfd_ddc *d, uint32_t channel, uint32_t *theta
   return hrfd::tuned_get_phase(d, "hrfd_ddc_get_phase", channel, theta);
 }
 
-// one launch over every channel on `s`: out_bytes per channel from R * out_bytes per capture
+extern "C" int hrfd_ddc_set_key_block(hrfd_ddc *d, uint32_t log2_samples)
+{
+  BANK_TRY(hrfd::ddc_key_check_block("hrfd_ddc_set_key_block", log2_samples));
+  BANK_TRY(hrfd::bank_need_handle("hrfd_ddc_set_key_block", d));
+  std::lock_guard<std::mutex> g(d->core.mu);
+  d->key_log2 = log2_samples;              // a launch takes its own copy; the key touches no state of the handle
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_ddc_n_keys(hrfd_ddc *d, uint32_t out_bytes, uint32_t *n)
+{
+  BANK_TRY(hrfd::ddc_key_check_result("hrfd_ddc_n_keys", n));
+  BANK_TRY(hrfd::bank_need_handle("hrfd_ddc_n_keys", d));
+  std::lock_guard<std::mutex> g(d->core.mu);
+  *n = hrfd::ddc_key_n(out_bytes / 2u, d->key_log2);
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_ddc_get_key_skips(hrfd_ddc *d, uint32_t channel, uint64_t *n)
+{
+  BANK_TRY(hrfd::ddc_key_check_result("hrfd_ddc_get_key_skips", n));
+  BANK_TRY(hrfd::bank_need_handle("hrfd_ddc_get_key_skips", d));
+  BANK_TRY(hrfd::ddc_key_check_channel("hrfd_ddc_get_key_skips", channel, d->n_channels));
+  HIP_TRY(hipSetDevice(d->core.device));
+  {
+    std::lock_guard<std::mutex> g(d->core.mu);
+    if (d->clear_history)
+    {
+      *n = 0;                              // no launch since create or reset
+      return HRFD_OK;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(d->core.last_stream));
+  const bool all = channel == HRFD_ALL_CHANNELS;
+  std::vector<unsigned long long> v(all ? d->n_channels : 1u);
+  HIP_TRY(hipMemcpy(v.data(), d->d_skips + (all ? 0u : channel), sizeof(unsigned long long) * v.size(), hipMemcpyDeviceToHost));
+  uint64_t sum = 0;
+  for (unsigned long long x : v)
+  {
+    sum += x;
+  }
+  *n = sum;
+  return HRFD_OK;
+}
+
+extern "C" int hrfd_ddc_count_key_skips(const uint8_t *key, uint64_t key_stride, uint32_t n_channels, uint32_t out_bytes,
+                                        uint32_t log2_samples, uint64_t *per_channel, uint64_t *sum)
+{
+  const char *who = "hrfd_ddc_count_key_skips";
+  BANK_TRY(hrfd::ddc_key_check_block(who, log2_samples));
+  if (key == nullptr || n_channels == 0 || out_bytes < 2u)
+  {
+    return fail(HRFD_EINVAL, "%s: need key rows, n_channels > 0 and out_bytes >= 2", who);
+  }
+  BANK_TRY(hrfd::ddc_key_check_result(who, sum));
+  BANK_TRY(hrfd::ddc_key_check_stride(who, key, key_stride, out_bytes, log2_samples));
+  *sum = hrfd::ddc_key_count_skips(key, key_stride, n_channels, out_bytes / 2u, log2_samples, per_channel);
+  return HRFD_OK;
+}
+
+// the key block of a call that starts now: a setter on another thread lands before or behind it
+static uint32_t ddc_key_log2(hrfd_ddc *d)
+{
+  std::lock_guard<std::mutex> g(d->core.mu);
+  return d->key_log2;
+}
+
+// one launch over every channel on `s`: out_bytes per channel from R * out_bytes per capture; d_key NULL: the unkeyed kernel
 static int ddc_launch(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_stride, uint32_t out_bytes, int8_t *d_out,
-                      uint64_t out_stride, hipStream_t s)
+                      uint64_t out_stride, hipStream_t s, const uint8_t *d_key = nullptr, uint64_t key_stride = 0,
+                      uint32_t key_log2 = hrfd::kDdcKeyDefaultLog2)
 {
   using namespace hrfd;
   // without this wait, the launch would read the history the last one is still writing
@@ -519,6 +638,7 @@ static int ddc_launch(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_st
       if (d->clear_history)
       {
         HIP_TRY(hipMemsetAsync(d->d_hist[d->cur], 0, (size_t)d->n_captures * d->H * 2, s));
+        HIP_TRY(hipMemsetAsync(d->d_skips, 0, sizeof(unsigned long long) * d->n_channels, s));
         d->clear_history = false;
       }
       d->dirty = false;
@@ -544,13 +664,30 @@ static int ddc_launch(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_st
   P.H = d->H;
   P.JA = bank_packed_len(P.TA);
   P.JB = bank_packed_len(P.TB);
+  P.key = d_key;
+  P.key_stride = key_stride;
+  P.key_log2 = key_log2;
+  P.skips = d->d_skips;
   const dim3 grid(P.n_tiles * d->n_channels + d->n_captures);
-  switch (d->R)
+  if (d_key == nullptr)
   {
-  case 1: hipLaunchKernelGGL(k_ddc<1>, grid, dim3(kDdcThreads), 0, s, P); break;
-  case 2: hipLaunchKernelGGL(k_ddc<2>, grid, dim3(kDdcThreads), 0, s, P); break;
-  case 4: hipLaunchKernelGGL(k_ddc<4>, grid, dim3(kDdcThreads), 0, s, P); break;
-  default: hipLaunchKernelGGL(k_ddc<8>, grid, dim3(kDdcThreads), 0, s, P); break;
+    switch (d->R)
+    {
+    case 1: hipLaunchKernelGGL((k_ddc<1, false>), grid, dim3(kDdcThreads), 0, s, P); break;
+    case 2: hipLaunchKernelGGL((k_ddc<2, false>), grid, dim3(kDdcThreads), 0, s, P); break;
+    case 4: hipLaunchKernelGGL((k_ddc<4, false>), grid, dim3(kDdcThreads), 0, s, P); break;
+    default: hipLaunchKernelGGL((k_ddc<8, false>), grid, dim3(kDdcThreads), 0, s, P); break;
+    }
+  }
+  else
+  {
+    switch (d->R)
+    {
+    case 1: hipLaunchKernelGGL((k_ddc<1, true>), grid, dim3(kDdcThreads), 0, s, P); break;
+    case 2: hipLaunchKernelGGL((k_ddc<2, true>), grid, dim3(kDdcThreads), 0, s, P); break;
+    case 4: hipLaunchKernelGGL((k_ddc<4, true>), grid, dim3(kDdcThreads), 0, s, P); break;
+    default: hipLaunchKernelGGL((k_ddc<8, true>), grid, dim3(kDdcThreads), 0, s, P); break;
+    }
   }
   const int rc = bank_launch_ok("k_ddc");
   if (rc != HRFD_OK)
@@ -576,50 +713,69 @@ static int ddc_check_call(hrfd_ddc *d, const void *captures, uint64_t capture_st
                                d->n_captures);
 }
 
-extern "C" int hrfd_ddc_process_device(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_stride, uint32_t out_bytes,
-                                       int8_t *d_out, uint64_t out_stride, void *stream)
+// The three entries, with and without a key (key NULL: the unkeyed call), under `who`.  The key's stride is checked against
+// the largest key block first, which needs no handle, then against the handle's; *k is the block the launch uses
+static int ddc_check_keyed(hrfd_ddc *d, const void *captures, uint64_t capture_stride, uint32_t out_bytes, const void *out,
+                           uint64_t out_stride, const void *key, uint64_t key_stride, const char *who, uint32_t *k)
 {
-  BANK_TRY(ddc_check_call(d, d_captures, capture_stride, out_bytes, d_out, out_stride, "hrfd_ddc_process_device"));
-  HIP_TRY(hipSetDevice(d->core.device));
-  return ddc_launch(d, d_captures, capture_stride, out_bytes, d_out, out_stride, d->core.stream_or_own(stream));
+  BANK_TRY(hrfd::ddc_key_check_stride(who, key, key_stride, out_bytes, hrfd::kDdcKeyMaxLog2));
+  BANK_TRY(ddc_check_call(d, captures, capture_stride, out_bytes, out, out_stride, who));
+  *k = ddc_key_log2(d);
+  return hrfd::ddc_key_check_stride(who, key, key_stride, out_bytes, *k);
 }
 
-extern "C" int hrfd_ddc_process(hrfd_ddc *d, const int8_t *captures, uint32_t out_bytes, int8_t *out)
+static int ddc_process_device(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_stride, uint32_t out_bytes,
+                              const uint8_t *d_key, uint64_t key_stride, int8_t *d_out, uint64_t out_stride, void *stream,
+                              const char *who)
 {
-  BANK_TRY(ddc_check_call(d, captures, d ? (uint64_t)d->R * out_bytes : 0, out_bytes, out, out_bytes, "hrfd_ddc_process"));
+  uint32_t k = 0;
+  BANK_TRY(ddc_check_keyed(d, d_captures, capture_stride, out_bytes, d_out, out_stride, d_key, key_stride, who, &k));
+  HIP_TRY(hipSetDevice(d->core.device));
+  return ddc_launch(d, d_captures, capture_stride, out_bytes, d_out, out_stride, d->core.stream_or_own(stream), d_key,
+                    key_stride, k);
+}
+
+static int ddc_process(hrfd_ddc *d, const int8_t *captures, uint32_t out_bytes, const uint8_t *key, int8_t *out, const char *who)
+{
+  uint32_t k = 0;
+  // the host entry's key is dense: rows of n_keys bytes
+  BANK_TRY(ddc_check_keyed(d, captures, d ? (uint64_t)d->R * out_bytes : 0, out_bytes, out, out_bytes, nullptr, 0, who, &k));
+  const uint32_t n_keys = hrfd::ddc_key_n(out_bytes / 2u, k);
   hrfd::BankHostCall call(d->core);
   const size_t in_bytes = (size_t)d->n_captures * d->R * out_bytes, out_total = (size_t)d->n_channels * out_bytes;
   const int8_t *d_in = call.up(d->d_in, captures, in_bytes);
+  const uint8_t *d_key = call.up(d->d_key, key, (size_t)d->n_channels * n_keys);
   int8_t *d_out = call.room(d->d_out, out, out_total);
   BANK_TRY(call.rc);
-  BANK_TRY(ddc_launch(d, d_in, (uint64_t)d->R * out_bytes, out_bytes, d_out, out_bytes, call.st));
+  BANK_TRY(ddc_launch(d, d_in, (uint64_t)d->R * out_bytes, out_bytes, d_out, out_bytes, call.st, d_key, n_keys, k));
   call.down(out, d_out, out_total);
   return call.finish();
 }
 
-extern "C" int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captures, uint64_t capture_stride,
-                                uint32_t block_bytes, uint32_t n_blocks, uint32_t gain_db, int16_t *d_pcm, uint32_t *d_n_pcm,
-                                uint32_t *d_magnitude, uint8_t *d_signal_allowed, uint32_t *n_replayed)
+static int ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captures, uint64_t capture_stride, uint32_t block_bytes,
+                       uint32_t n_blocks, const uint8_t *d_key, uint64_t key_stride, uint32_t gain_db, int16_t *d_pcm,
+                       uint32_t *d_n_pcm, uint32_t *d_magnitude, uint8_t *d_signal_allowed, uint32_t *n_replayed, const char *who)
 {
   if (rx == nullptr || d_pcm == nullptr || d_n_pcm == nullptr)
   {
-    return fail(HRFD_EINVAL, "hrfd_ddc_receive: NULL argument");
+    return fail(HRFD_EINVAL, "%s: NULL argument", who);
   }
   if (d != nullptr && rx->n_channels != d->n_channels)
   {
-    return fail(HRFD_EINVAL, "hrfd_ddc_receive: the rx handle has %u channels, the DDC %u", rx->n_channels, d->n_channels);
+    return fail(HRFD_EINVAL, "%s: the rx handle has %u channels, the DDC %u", who, rx->n_channels, d->n_channels);
   }
   if (block_bytes == 0 || (block_bytes & 1u) != 0 || block_bytes > HRFD_BLOCK_BYTES || n_blocks == 0 ||
       (uint64_t)block_bytes * n_blocks > (1u << 25))
   {
-    return fail(HRFD_EINVAL, "hrfd_ddc_receive: block_bytes must be even, > 0 and <= %u, n_blocks > 0, at most 2^25 "
-                "bytes per channel (got %u x %u)", HRFD_BLOCK_BYTES, block_bytes, n_blocks);
+    return fail(HRFD_EINVAL, "%s: block_bytes must be even, > 0 and <= %u, n_blocks > 0, at most 2^25 "
+                "bytes per channel (got %u x %u)", who, HRFD_BLOCK_BYTES, block_bytes, n_blocks);
   }
   const uint32_t out_bytes = block_bytes * n_blocks;
-  BANK_TRY(ddc_check_call(d, d_captures, capture_stride, out_bytes, d_pcm, out_bytes, "hrfd_ddc_receive"));
+  uint32_t k = 0;
+  BANK_TRY(ddc_check_keyed(d, d_captures, capture_stride, out_bytes, d_pcm, out_bytes, d_key, key_stride, who, &k));
   if (rx->device != d->core.device)
   {
-    return fail(HRFD_EINVAL, "hrfd_ddc_receive: the rx handle lives on device %d, the DDC on %d", rx->device, d->core.device);
+    return fail(HRFD_EINVAL, "%s: the rx handle lives on device %d, the DDC on %d", who, rx->device, d->core.device);
   }
   HIP_TRY(hipSetDevice(d->core.device));
   hipStream_t s = rx->stream;
@@ -634,7 +790,8 @@ extern "C" int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captur
   }
   uint32_t *mag = d_magnitude ? d_magnitude : (uint32_t *)d->d_scratch_mag.p;
   uint8_t *allowed = d_signal_allowed ? d_signal_allowed : d->d_scratch_mag + units * 4;
-  BANK_TRY(ddc_launch(d, d_captures, capture_stride, out_bytes, d->d_rx, out_bytes, s));
+  // the rx bank runs over every channel, keyed or not: its state moves on over a keyed-off block's zeros
+  BANK_TRY(ddc_launch(d, d_captures, capture_stride, out_bytes, d->d_rx, out_bytes, s, d_key, key_stride, k));
   // mode NONE / squelched units produce no PCM: zeros, as hrfd_rx_process_block hands back
   HIP_TRY(hipMemsetAsync(d_pcm, 0, units * ((block_bytes + 511u) / 512u) * sizeof(int16_t), s));
   uint32_t replayed = 0;
@@ -646,4 +803,46 @@ extern "C" int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captur
     *n_replayed = replayed;
   }
   return HRFD_OK;
+}
+
+extern "C" int hrfd_ddc_process_device(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_stride, uint32_t out_bytes,
+                                       int8_t *d_out, uint64_t out_stride, void *stream)
+{
+  return ddc_process_device(d, d_captures, capture_stride, out_bytes, nullptr, 0, d_out, out_stride, stream,
+                            "hrfd_ddc_process_device");
+}
+
+extern "C" int hrfd_ddc_process_device_keyed(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_stride, uint32_t out_bytes,
+                                             const uint8_t *d_key, uint64_t key_stride, int8_t *d_out, uint64_t out_stride,
+                                             void *stream)
+{
+  return ddc_process_device(d, d_captures, capture_stride, out_bytes, d_key, key_stride, d_out, out_stride, stream,
+                            "hrfd_ddc_process_device_keyed");
+}
+
+extern "C" int hrfd_ddc_process(hrfd_ddc *d, const int8_t *captures, uint32_t out_bytes, int8_t *out)
+{
+  return ddc_process(d, captures, out_bytes, nullptr, out, "hrfd_ddc_process");
+}
+
+extern "C" int hrfd_ddc_process_keyed(hrfd_ddc *d, const int8_t *captures, uint32_t out_bytes, const uint8_t *key, int8_t *out)
+{
+  return ddc_process(d, captures, out_bytes, key, out, "hrfd_ddc_process_keyed");
+}
+
+extern "C" int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captures, uint64_t capture_stride,
+                                uint32_t block_bytes, uint32_t n_blocks, uint32_t gain_db, int16_t *d_pcm, uint32_t *d_n_pcm,
+                                uint32_t *d_magnitude, uint8_t *d_signal_allowed, uint32_t *n_replayed)
+{
+  return ddc_receive(d, rx, d_captures, capture_stride, block_bytes, n_blocks, nullptr, 0, gain_db, d_pcm, d_n_pcm, d_magnitude,
+                     d_signal_allowed, n_replayed, "hrfd_ddc_receive");
+}
+
+extern "C" int hrfd_ddc_receive_keyed(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captures, uint64_t capture_stride,
+                                      uint32_t block_bytes, uint32_t n_blocks, const uint8_t *d_key, uint64_t key_stride,
+                                      uint32_t gain_db, int16_t *d_pcm, uint32_t *d_n_pcm, uint32_t *d_magnitude,
+                                      uint8_t *d_signal_allowed, uint32_t *n_replayed)
+{
+  return ddc_receive(d, rx, d_captures, capture_stride, block_bytes, n_blocks, d_key, key_stride, gain_db, d_pcm, d_n_pcm,
+                     d_magnitude, d_signal_allowed, n_replayed, "hrfd_ddc_receive_keyed");
 }

@@ -416,11 +416,42 @@ int hrfd_nco_run(hrfd_nco *h, int fast, uint32_t count, float *i_out, float *q_o
  *                             64 blocks and the exact replay of channels that failed their speculation (*n_replayed, may
  *                             be NULL).  d_pcm [C][n_blocks][hrfd_rx_pcm_capacity(block_bytes)], d_n_pcm / d_magnitude /
  *                             d_signal_allowed [C][n_blocks] on the device (the last two may be NULL); blocking.
+ *
+ * The receive key (listen only where someone transmits).  The *_keyed calls take, besides the captures, a key row per
+ * channel: uint8 [C][n_keys], rows key_stride bytes apart at any address, n_keys = ceil(M / 2^k) for the M = out_bytes / 2
+ * output samples per channel of the call.  k is the handle's key block, 10..17 (hrfd_ddc_set_key_block; default 17: 131072
+ * output samples = 262144 bytes = one rx block = 512 PCM samples, the granularity of the spectrum bank's present[b] when it
+ * is asked once per block).  Key byte j of a row covers the call-local output samples [j 2^k, (j + 1) 2^k); any non-zero byte
+ * is "on":
+ *   outk[c][m] = key[c][m >> k] != 0 ? out[c][m] : (0, 0)  (0 <= m < M, call-local; out is what the unkeyed call writes)
+ * Everything else a keyed call leaves behind is exactly what the unkeyed call leaves behind: the captures' history, N, and
+ * every byte outside the 2 M bytes of each output row.  The key does not touch the handle's state: the DDC carries nothing
+ * per channel through time (the history is the capture's, the phase a function of N), so a channel that is keyed on again
+ * is at once what it would have been.  A NULL key is the unkeyed call.  The key is read for 0 <= m < M only.
+ *   work      the kernel owns one (channel, tile of 1024 outputs) per workgroup; tiles are call-local, so a tile lies in one
+ *             key block.  The unit (channel c, tile t) is skipped iff key[c][(1024 t) >> k] == 0.  A skipped unit loads
+ *             neither the cosine table nor the taps, nothing of the capture or its history, runs no mixer and no FIR; it
+ *             stores the 2 cnt zero bytes of its cnt outputs (the last tile may be short), whatever the row's base address
+ *             and stride, and adds 1 to the skip meter of channel c.  The workgroups that keep the captures' history know no
+ *             key.
+ *   hrfd_ddc_set_key_block    log2 of the key block in output samples, 10..17; from the next call on
+ *   hrfd_ddc_n_keys           n_keys of a call of out_bytes under the handle's key block
+ *   hrfd_ddc_get_key_skips    waits for the handle's last launch, then reads the units of one channel skipped since create /
+ *                             reset (uint64), or their sum over the bank (HRFD_ALL_CHANNELS): the idle share of its work
+ *   hrfd_ddc_count_key_skips  host only, no handle: what one call of out_bytes with these key rows (host memory) adds to the
+ *                             meters under key block k, counted unit by unit; per_channel [n_channels] may be NULL.  Not
+ *                             part of the key's working interface: it is exported so that the tests, and a caller who
+ *                             wants to predict the meters, reach the one statement of the skip rule (hrfd_ddc_key.h)
+ *   hrfd_ddc_process_keyed    hrfd_ddc_process with key [C][n_keys], dense
+ *   hrfd_ddc_process_device_keyed   hrfd_ddc_process_device with d_key, rows key_stride >= n_keys apart
+ *   hrfd_ddc_receive_keyed    hrfd_ddc_receive with d_key: outputs exactly those of hrfd_ddc_process_device_keyed followed by
+ *                             hrfd_rx_process_block.  The rx bank runs over every channel as in hrfd_ddc_receive: its state
+ *                             moves on over a keyed-off block's zeros
  */
 typedef struct hrfd_ddc hrfd_ddc;
 int hrfd_ddc_create(uint32_t n_captures, uint32_t n_channels, uint32_t decimation, int device, hrfd_ddc **out);
 int hrfd_ddc_destroy(hrfd_ddc *d);
-int hrfd_ddc_reset(hrfd_ddc *d);                                   /* history 0, N = 0, every theta_ref = N_ref = 0 */
+int hrfd_ddc_reset(hrfd_ddc *d);              /* history 0, N = 0, every theta_ref = N_ref = 0, skip meters 0 */
 int hrfd_ddc_set_tuning(hrfd_ddc *d, uint32_t channel, uint32_t capture, uint32_t step);
 int hrfd_ddc_set_gain_shift(hrfd_ddc *d, uint32_t channel, uint32_t g);          /* HRFD_ALL_CHANNELS allowed */
 int hrfd_ddc_set_filter(hrfd_ddc *d, int stage, const int16_t *taps, uint32_t n); /* stage 0 = A, 1 = B; n = 0: bypass */
@@ -431,6 +462,17 @@ int hrfd_ddc_process_device(hrfd_ddc *d, const int8_t *d_captures, uint64_t capt
 int hrfd_ddc_receive(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captures, uint64_t capture_stride,
                      uint32_t block_bytes, uint32_t n_blocks, uint32_t gain_db, int16_t *d_pcm, uint32_t *d_n_pcm,
                      uint32_t *d_magnitude, uint8_t *d_signal_allowed, uint32_t *n_replayed);
+int hrfd_ddc_set_key_block(hrfd_ddc *d, uint32_t log2_samples);                  /* 10..17, default 17 */
+int hrfd_ddc_n_keys(hrfd_ddc *d, uint32_t out_bytes, uint32_t *n);
+int hrfd_ddc_get_key_skips(hrfd_ddc *d, uint32_t channel, uint64_t *n);          /* HRFD_ALL_CHANNELS: the sum */
+int hrfd_ddc_count_key_skips(const uint8_t *key, uint64_t key_stride, uint32_t n_channels, uint32_t out_bytes,
+                             uint32_t log2_samples, uint64_t *per_channel, uint64_t *sum);
+int hrfd_ddc_process_keyed(hrfd_ddc *d, const int8_t *captures, uint32_t out_bytes, const uint8_t *key, int8_t *out);
+int hrfd_ddc_process_device_keyed(hrfd_ddc *d, const int8_t *d_captures, uint64_t capture_stride, uint32_t out_bytes,
+                                  const uint8_t *d_key, uint64_t key_stride, int8_t *d_out, uint64_t out_stride, void *stream);
+int hrfd_ddc_receive_keyed(hrfd_ddc *d, hrfd_rx *rx, const int8_t *d_captures, uint64_t capture_stride, uint32_t block_bytes,
+                           uint32_t n_blocks, const uint8_t *d_key, uint64_t key_stride, uint32_t gain_db, int16_t *d_pcm,
+                           uint32_t *d_n_pcm, uint32_t *d_magnitude, uint8_t *d_signal_allowed, uint32_t *n_replayed);
 
 /* ------------------------------------------------------------------------------
  * DUC bank: C channel streams at 2.048 MS/s -> W wideband captures (the DDC's mirror; the reference transmits one station
