@@ -324,6 +324,14 @@ def load() -> C.CDLL:
         L.hrfd_hdlc_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]
         L.hrfd_hdlc_debug_slow.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp]
         L.hrfd_hdlc_debug_max_out.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, _u32p]
+    if hasattr(L, "hrfd_hdlcgen_create"):                  # (an older build named by HRFD_LIB has no HDLC framer bank)
+        L.hrfd_hdlcgen_create.argtypes = [C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_hdlcgen_destroy.argtypes = [_vp]
+        L.hrfd_hdlcgen_set_flags.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.hrfd_hdlcgen_max_bits.argtypes = [_vp, C.c_uint32, C.c_uint64, _u32p]
+        L.hrfd_hdlcgen_process.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp]
+        L.hrfd_hdlcgen_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]
+        L.hrfd_hdlc_encode.argtypes = [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]
     L.hrfd_q15_table.argtypes = [C.c_char_p, _i16p, C.c_int]
     L.hrfd_atan2_table.argtypes = [_f32p]
     L.hrfd_dbfs_table.argtypes = [_i32p]

@@ -1864,6 +1864,179 @@ def hdlc_encode(payloads, n_lead_flags: int = 12, n_between: int = 2, n_tail_fla
     return np.array(out, dtype=np.uint8)
 
 
+HDLCGEN_MAX_BITS = 1 << 20
+HDLCGEN_MAX_FLAGS = 255
+
+
+def hdlc_records(payloads) -> np.ndarray:
+    """payloads -> one row of the HDLC bank's records (uint8): uint32 end_bit = 0, uint16 n_payload, uint16 fcs = 0, the
+    payload, zeros up to a multiple of 4.  The framer ignores end_bit and fcs"""
+    out = bytearray()
+    for p in payloads:
+        p = bytes(p)
+        if not 1 <= len(p) <= HDLC_MAX_PAYLOAD:
+            raise ValueError(f"a payload has 1..{HDLC_MAX_PAYLOAD} bytes, got {len(p)}")
+        out += (0).to_bytes(4, "little") + len(p).to_bytes(2, "little") + b"\0\0" + p + b"\0" * (-len(p) & 3)
+    return np.frombuffer(bytes(out), dtype=np.uint8).copy()
+
+
+def hdlcgen_max_bits(n_frames: int, payload_bytes: int, n_lead_flags: int = 12, n_between: int = 2, n_tail_flags: int = 3) -> int:
+    """a row of bits that never drops n_frames frames of payload_bytes together: D + D // 5 with D = 8 (payload_bytes +
+    2 n_frames), and the lead + (n_frames - 1) between + tail flags"""
+    D = 8 * (int(payload_bytes) + 2 * int(n_frames))
+    return D + D // 5 + 8 * (int(n_lead_flags) + (int(n_frames) - 1) * int(n_between) + int(n_tail_flags))
+
+
+def hdlc_encode_c(payloads, n_lead_flags: int = 12, n_between: int = 2, n_tail_flags: int = 3, max_bits: int = None,
+                  want_counts: bool = False):
+    """hdlc_encode through the library's host entry hrfd_hdlc_encode (no GPU): the same bits, from the C text that restates
+    the framer bank's law for one row.  max_bits: the row's room, the bound of the payloads unless given; frames that do
+    not fit are dropped under the bank's rule.  With want_counts also (n_sent, dropped)"""
+    payloads = [bytes(p) for p in payloads]
+    row = hdlc_records(payloads)
+    if row.size == 0:
+        row = np.zeros(4, dtype=np.uint8)
+    if max_bits is None:
+        max_bits = hdlcgen_max_bits(len(payloads), sum(len(p) for p in payloads), n_lead_flags, n_between, n_tail_flags) if payloads else 1
+    for name, v in (("n_lead_flags", n_lead_flags), ("n_between", n_between), ("n_tail_flags", n_tail_flags), ("max_bits", max_bits)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{name} must fit uint32, got {v}")
+    bits = np.zeros(min(int(max_bits), HDLCGEN_MAX_BITS), dtype=np.uint8)
+    n_bits, n_sent, dropped = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    check(_lib.load().hrfd_hdlc_encode(_ptr(row), row.size, len(payloads), int(n_lead_flags), int(n_between), int(n_tail_flags),
+                                       _ptr(bits), int(max_bits), C.byref(n_bits), C.byref(n_sent), C.byref(dropped)),
+          "hrfd_hdlc_encode")
+    out = bits[:n_bits.value].copy()
+    return (out, (int(n_sent.value), int(dropped.value))) if want_counts else out
+
+
+class HdlcGen(_Bank):
+    """The HDLC framer bank (hrfd_hdlcgen_*): rows of frame records in, read where they lie on the device (Hdlc's own rows
+    among them), the bits that say them out: per channel a row of one byte per bit, flags, the CRC-16/X.25 check sequence and
+    bit stuffing included, as AfskGen.queue takes it and Hdlc reads it; for the same flag counts hdlc_encode bit for bit.
+    A frame that does not fit a row's max_bits is dropped with every frame behind it and counted.  The bank keeps nothing
+    between calls.  (One launch of one workgroup per channel, so like Hdlc it has no chunked launch and no
+    debug_set_max_wgs.)"""
+
+    _prefix = "hdlcgen"
+
+    def __init__(self, n_channels: int, n_lead_flags: int = 12, n_between: int = 2, n_tail_flags: int = 3, device: int = 0):
+        self.n = int(n_channels)
+        self._create(self.n, device)
+        if (int(n_lead_flags), int(n_between), int(n_tail_flags)) != (12, 2, 3):
+            self.set_flags(n_lead_flags, n_between, n_tail_flags)
+
+    def set_flags(self, n_lead_flags: int = 12, n_between: int = 2, n_tail_flags: int = 3):
+        """flags in front of the first frame (0..255), between two frames and behind the last (1..255 each)"""
+        for name, v in (("n_lead_flags", n_lead_flags), ("n_between", n_between), ("n_tail_flags", n_tail_flags)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} must fit uint32, got {v}")
+        self._call("set_flags", int(n_lead_flags), int(n_between), int(n_tail_flags))
+
+    def max_bits(self, n_frames: int, payload_bytes: int) -> int:
+        """a row of bits that never drops n_frames frames of payload_bytes together under the handle's flag counts"""
+        v = C.c_uint32(0)
+        self._call("max_bits", int(n_frames), int(payload_bytes), C.byref(v))
+        return int(v.value)
+
+    def pack(self, payloads_per_channel):
+        """per channel a list of payloads -> (rows uint8 [n_channels, in_bytes] of records, n_frames uint32 [n_channels])"""
+        if len(payloads_per_channel) != self.n:
+            raise ValueError(f"need the payloads of {self.n} channels, got {len(payloads_per_channel)}")
+        recs = [hdlc_records(p) for p in payloads_per_channel]
+        rows = np.zeros((self.n, max(4, max(r.size for r in recs))), dtype=np.uint8)
+        for c, r in enumerate(recs):
+            rows[c, :r.size] = r
+        return rows, np.array([len(p) for p in payloads_per_channel], dtype=np.uint32)
+
+    def process(self, payloads_per_channel, max_bits: int = None, want_counts: bool = False):
+        """per channel a list of payloads -> per channel the bits (uint8, 0 / 1) of one message that says them; with
+        want_counts also (n_sent, dropped), uint32 [n_channels] each.  max_bits: a row's room, the bound of the longest
+        channel unless given; blocking"""
+        rows, n_frames = self.pack(payloads_per_channel)
+        if max_bits is None:
+            max_bits = max([1] + [self.max_bits(len(p), sum(len(bytes(q)) for q in p)) for p in payloads_per_channel if len(p)])
+        bits, (n_bits, n_sent, dropped) = self.process_rows(rows, n_frames, int(max_bits))
+        out = [bits[c, :n_bits[c]].copy() for c in range(self.n)]
+        return (out, (n_sent, dropped)) if want_counts else out
+
+    def process_rows(self, rows: np.ndarray, n_frames, max_bits: int):
+        """rows uint8 [n_channels, in_bytes] of records (pack's, or Hdlc's), n_frames uint32 [n_channels] -> (bits uint8
+        [n_channels, max_bits], (n_bits, n_sent, dropped)); blocking"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8).reshape(self.n, -1)
+        nf = np.ascontiguousarray(n_frames, dtype=np.uint32).reshape(self.n)
+        bits = np.zeros((self.n, int(max_bits)), dtype=np.uint8)
+        n_bits, n_sent, dropped = (np.zeros(self.n, dtype=np.uint32) for _ in range(3))
+        self._call("process", _ptr(rows), rows.shape[1], _ptr(nf), _ptr(bits), int(max_bits), _ptr(n_bits), _ptr(n_sent), _ptr(dropped))
+        return bits, (n_bits, n_sent, dropped)
+
+    def process_device(self, d_in, in_stride: int, in_bytes: int, d_n_frames, d_bits, bits_stride: int, max_bits: int, d_n_bits,
+                       d_n_sent=None, d_dropped=None, stream=None):
+        """device pointers (ints): rows of records in_stride apart of in_bytes each and their counts (Hdlc.process_device's
+        d_out and d_n_frames as they are); rows of bits bits_stride apart of max_bits each, and the counts; d_n_sent and
+        d_dropped may be None; asynchronous on stream (None = the handle's own)"""
+        self._call("process_device", _ptr(d_in), int(in_stride), int(in_bytes), _ptr(d_n_frames), _ptr(d_bits), int(bits_stride),
+                   int(max_bits), _ptr(d_n_bits), _ptr(d_n_sent), _ptr(d_dropped), _ptr(stream))
+
+
+def ax25_address(call: str, ssid: int = 0, last: bool = False) -> bytes:
+    """the seven bytes of an AX.25 address field: the call sign in capitals, filled up to six with spaces, every character
+    shifted left by one, then the SSID byte 0x60 | ssid << 1, with bit 0 set on the last address of the header"""
+    call = str(call).upper()
+    if not 1 <= len(call) <= 6 or not all(c.isascii() and c.isalnum() for c in call):
+        raise ValueError(f"a call sign has 1..6 letters and digits, got {call!r}")
+    if not 0 <= int(ssid) <= 15:
+        raise ValueError(f"ssid must be 0..15, got {ssid}")
+    return bytes(ord(c) << 1 for c in call.ljust(6)) + bytes([0x60 | (int(ssid) << 1) | (1 if last else 0)])
+
+
+def _ax25_station(s):
+    """a station as 'CALL', 'CALL-SSID' or (call, ssid) -> (call, ssid)"""
+    if isinstance(s, str):
+        call, _, ssid = s.partition("-")
+        return call, int(ssid) if ssid else 0
+    return str(s[0]), int(s[1])
+
+
+def ax25_ui_frame(dest, src, info, path=(), pid: int = 0xF0) -> bytes:
+    """the payload of an AX.25 UI frame (what APRS sends), without flags and check sequence, ready for HdlcGen or
+    hdlc_encode: destination, source and up to eight digipeaters ("CALL-SSID" or (call, ssid)), control 0x03, the PID
+    (0xF0: no layer 3) and the information field"""
+    path = list(path)
+    if len(path) > 8:
+        raise ValueError(f"at most 8 digipeaters, got {len(path)}")
+    if not 0 <= int(pid) <= 255:
+        raise ValueError(f"pid must be 0..255, got {pid}")
+    stations = [_ax25_station(s) for s in [dest, src] + path]
+    head = b"".join(ax25_address(c, s, last=(i + 1 == len(stations))) for i, (c, s) in enumerate(stations))
+    frame = head + bytes([0x03, int(pid)]) + bytes(info)
+    if len(frame) > HDLC_MAX_PAYLOAD:
+        raise ValueError(f"the frame has {len(frame)} bytes, more than {HDLC_MAX_PAYLOAD}")
+    return frame
+
+
+def ax25_parse(payload):
+    """the inverse of ax25_ui_frame: {"dest": (call, ssid), "src": (call, ssid), "path": [(call, ssid), ..], "control", "pid",
+    "info"}; ValueError for what is no UI frame (a header that does not end, control other than 0x03)"""
+    p = bytes(payload)
+    stations, at = [], 0
+    while True:
+        if at + 7 > len(p) or len(stations) == 10:
+            raise ValueError("the address field does not end")
+        a = p[at:at + 7]
+        if any(v & 1 for v in a[:6]):
+            raise ValueError("a call sign byte with its low bit set")
+        stations.append(("".join(chr(v >> 1) for v in a[:6]).rstrip(), (a[6] >> 1) & 15))
+        at += 7
+        if a[6] & 1:
+            break
+    if len(stations) < 2 or at + 2 > len(p):
+        raise ValueError("no destination and source, or no control and PID behind them")
+    if p[at] != 0x03:
+        raise ValueError(f"control 0x{p[at]:02X} is no UI frame")
+    return {"dest": stations[0], "src": stations[1], "path": stations[2:], "control": p[at], "pid": p[at + 1], "info": p[at + 2:]}
+
+
 class AfskGen(_GenBank):
     """The AFSK generator bank (hrfd_afskgen_*): packet data on the PCM of n_channels transmit channels, the mirror of Afsk.
     Messages of up to 8192 bits, each with a modem of its own (Bell 202 by default), are queued per channel at absolute
@@ -1899,6 +2072,21 @@ class AfskGen(_GenBank):
     def send(self, channel: int, payloads, **modem):
         """queue(channel, hdlc_encode(payloads), ...): one message of HDLC frames with the default flag counts"""
         self.queue(channel, hdlc_encode(payloads), **modem)
+
+    def send_all(self, framer, payloads_per_channel, **modem):
+        """the whole bank's packets at once: one framer call (an HdlcGen of as many channels) frames every channel's
+        payloads on the device, then one queue per channel that has a frame.  Refused before anything is queued if a
+        channel's message passes 8192 bits"""
+        if framer.n != self.n:
+            raise ValueError(f"the framer has {framer.n} channels, the generator {self.n}")
+        messages, (_, dropped) = framer.process(payloads_per_channel, want_counts=True)
+        for c, m in enumerate(messages):
+            if m.size > AFSKGEN_MAX_BITS or dropped[c]:
+                raise ValueError(f"channel {c}: a message of {m.size} bits ({int(dropped[c])} frames dropped); a message has at most "
+                                 f"{AFSKGEN_MAX_BITS} bits")
+        for c, m in enumerate(messages):
+            if m.size:
+                self.queue(c, m, **modem)
 
     def cut(self, channel: int = ALL):
         """ramp the message in progress down over the next 64 samples and drop those not yet begun"""

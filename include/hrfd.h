@@ -1257,6 +1257,64 @@ int hrfd_hdlc_process_device(hrfd_hdlc *h, const uint8_t *d_bits, uint64_t bits_
                              uint32_t *d_n_bad, uint32_t *d_dropped, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * HDLC framer bank: the packet frames of C channels -> the bits that say them, on the device: flags, the CRC-16/X.25 frame
+ * check and bit stuffing.  The mirror of the HDLC bank: it reads rows of that bank's records where they lie and writes rows of
+ * bits in the format hrfd_afskgen_queue takes and hrfd_hdlc_* reads.  The law is per channel, the same on every device
+ * (tests/hdlcgen_model.py restates it):
+ *   sizes     C = 1..65536 channels, fixed at create.  Per call in_bytes, a multiple of 4 (at least 4), and max_bits =
+ *             1..HRFD_HDLCGEN_MAX_BITS = 2^20.  Three flag counts in the handle: lead 0..255, between 1..255, tail 1..255.
+ *   input     per channel a row of in_bytes bytes of hrfd_hdlc_record: uint32 end_bit, uint16 n_payload, uint16 fcs, the
+ *             payload, zeros up to a multiple of 4.  end_bit and fcs are ignored: the check sequence is always computed anew,
+ *             so a row hrfd_hdlc_process_device wrote, with its d_n_frames, is framed again where it lies.  Rows are
+ *             in_stride_bytes apart (a multiple of 4, >= in_bytes) and 4-byte aligned.  d_n_frames [C] says how many records
+ *             a row holds; it is read on the device: no call waits for it.
+ *   row       one byte per bit, 0 or 1: `lead` flags 0x7E; per frame the payload and its CRC-16/X.25 (reflected 0x1021 from
+ *             0xFFFF, inverted), low byte first, every byte LSB first, with a zero inserted behind every fifth consecutive
+ *             one: the count of ones starts at 0 at the frame's first bit and runs through the check sequence, and a fifth
+ *             one that is the frame's last bit is followed by a zero as well; `between` flags between two frames, `tail`
+ *             flags behind the last.  For the same flag counts this is api.hdlc_encode, bit for bit.  A channel that sends
+ *             no frame writes nothing and has n_bits = 0.
+ *   fit       frames are taken in row order.  The walk of a row ends at the first record that is malformed (its header or
+ *             payload runs past in_bytes, or n_payload is outside 1..HRFD_HDLC_MAX_PAYLOAD) and at the first frame whose
+ *             bits, with the flags in front of it and the tail flags still to come, would pass max_bits.  That frame and
+ *             every one behind it are not sent: d_dropped [C] = d_n_frames - d_n_sent; d_n_sent [C] counts the frames
+ *             framed, d_n_bits [C] is the row's length.  Bytes of a row behind n_bits are not written.
+ *   bound     D = 8 (payload_bytes + 2 n_frames) data bits take at most D + floor(D / 5) bits (a frame of D_i data bits
+ *             takes at most D_i + floor(D_i / 5), and the floors' sum is at most the sum's floor); with the
+ *             lead + (n_frames - 1) between + tail flags that is a max_bits that never drops.
+ *   defaults  lead 12, between 2, tail 3 (api.hdlc_encode's).
+ * The bank carries nothing from call to call: a call's output is a complete message.  Arguments are checked before any
+ * device is touched (HRFD_EINVAL without a GPU as well).  Setters never wait for the device: the flag counts travel with the
+ * next launch.  Calls may use different streams: each launch is ordered on the device behind the handle's previous one, so
+ * a call chains behind the hrfd_hdlc_process_device call, or the copy, that filled its input when both are given the same
+ * stream.
+ *   hrfd_hdlcgen_set_flags        the three flag counts, from the next call on
+ *   hrfd_hdlcgen_max_bits         the bound above for n_frames frames (at least 1) of payload_bytes together under the
+ *                                 handle's flag counts; refused if it passes 2^20
+ *   hrfd_hdlcgen_process          host buffers, dense: records [C][in_bytes], n_frames [C] -> bits [C][max_bits], n_bits [C],
+ *                                 n_sent [C] or NULL, dropped [C] or NULL; blocking
+ *   hrfd_hdlcgen_process_device   device buffers; d_bits at any address, bits_stride_bytes >= max_bits; the counts dense
+ *                                 and 4-byte aligned; d_n_sent and d_dropped may be NULL.  A row of bits may not overlap
+ *                                 the records.  Asynchronous on `stream` (a hipStream_t, NULL = the handle's own)
+ *   hrfd_hdlc_encode              one row under the same law on the host, bit by bit: no handle, no device.  records
+ *                                 4-byte aligned, n_sent and dropped may be NULL; bits may not overlap the records
+ */
+typedef struct hrfd_hdlcgen hrfd_hdlcgen;
+#define HRFD_HDLCGEN_MAX_BITS (1u << 20)
+#define HRFD_HDLCGEN_MAX_FLAGS 255
+int hrfd_hdlcgen_create(uint32_t n_channels, int device, hrfd_hdlcgen **out);
+int hrfd_hdlcgen_destroy(hrfd_hdlcgen *h);
+int hrfd_hdlcgen_set_flags(hrfd_hdlcgen *h, uint32_t n_lead_flags, uint32_t n_between, uint32_t n_tail_flags);
+int hrfd_hdlcgen_max_bits(hrfd_hdlcgen *h, uint32_t n_frames, uint64_t payload_bytes, uint32_t *max_bits);
+int hrfd_hdlcgen_process(hrfd_hdlcgen *h, const uint8_t *records, uint32_t in_bytes, const uint32_t *n_frames, uint8_t *bits,
+                         uint32_t max_bits, uint32_t *n_bits, uint32_t *n_sent, uint32_t *dropped);
+int hrfd_hdlcgen_process_device(hrfd_hdlcgen *h, const uint8_t *d_in, uint64_t in_stride_bytes, uint32_t in_bytes,
+                                const uint32_t *d_n_frames, uint8_t *d_bits, uint64_t bits_stride_bytes, uint32_t max_bits,
+                                uint32_t *d_n_bits, uint32_t *d_n_sent, uint32_t *d_dropped, void *stream);
+int hrfd_hdlc_encode(const uint8_t *records, uint32_t in_bytes, uint32_t n_frames, uint32_t lead, uint32_t between, uint32_t tail,
+                     uint8_t *bits, uint32_t max_bits, uint32_t *n_bits, uint32_t *n_sent, uint32_t *dropped);
+
+/* ------------------------------------------------------------------------------
  * Introspection used by the tests: copy out the constant tables the kernels use.
  * name: "HB1","HB2","HB3","WBFM_D1","POST_D12","AUDIO_D40","FM_TUNER_D32","AM_D1",
  * "AM_D2","AM_D3","SSB_DELAY","SSB_HILBERT","INTERP_HB8","INTERP_HB3","INTERP_HB2",
