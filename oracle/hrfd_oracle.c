@@ -776,20 +776,15 @@ static int32_t magnitude_to_dbfs(uint32_t magnitude)
   return v;
 }
 
-uint32_t orc_rx_process(orc_rx *h, const int8_t *iq, uint32_t bytes, uint32_t gain_db,
-                        int16_t *pcm, uint32_t pcm_cap, uint32_t *magnitude,
-                        int *signal_allowed, int8_t *iq256_out)
+/* A2 + A4: the front end of one call.  dec: room for bytes / 8 + 16 bytes; returns the call's decimatedByteCount. */
+static uint32_t rx_front_end(orc_rx *h, const int8_t *iq, uint32_t bytes, int8_t *dec)
 {
   uint32_t n_in = bytes / 2;
-  uint32_t n3 = 0, dec_bytes, n_pcm = 0;
+  uint32_t n3 = 0, dec_bytes;
   int16_t *x = (int16_t *)malloc(((size_t)n_in + 1) * sizeof(int16_t));
   int16_t *t1 = (int16_t *)malloc(((size_t)n_in / 2 + 2) * sizeof(int16_t));
   int16_t *t2 = (int16_t *)malloc(((size_t)n_in / 4 + 2) * sizeof(int16_t));
   int16_t *t3 = (int16_t *)malloc(((size_t)n_in / 8 + 2) * sizeof(int16_t));
-  int8_t *dec = (int8_t *)calloc((size_t)n_in / 4 + 16, 1);
-  int present, allowed;
-  uint32_t mag_sum = 0, mag_n;
-  int32_t dbfs;
 
   /* A2: IqDataProcessor::reduceSampleRate (:429-500): three half-band /2 stages
    * per rail, (int8_t) narrowing, re-interleave. */
@@ -821,6 +816,46 @@ uint32_t orc_rx_process(orc_rx *h, const int8_t *iq, uint32_t bytes, uint32_t ga
     a = dec[i + 6]; b = dec[i + 7];
     dec[i + 6] = b; dec[i + 7] = (int8_t)(uint8_t)(0u - (uint8_t)a);
   }
+  free(x); free(t1); free(t2); free(t3);
+  return dec_bytes;
+}
+
+/* IqDataProcessor::reduceSampleRate as a call of its own (with the Fs/4 mix, like hrfd_rx_reduce_sample_rate): the bytes
+ * a mode-None call dumps, but neither the squelch nor a demodulator sees the block.  Returns the byte count. */
+uint32_t orc_rx_reduce_sample_rate(orc_rx *h, const int8_t *iq, uint32_t bytes, int8_t *iq256_out)
+{
+  int8_t *dec = (int8_t *)calloc((size_t)bytes / 8 + 16, 1);
+  uint32_t dec_bytes = rx_front_end(h, iq, bytes, dec);
+  memcpy(iq256_out, dec, dec_bytes);
+  free(dec);
+  return dec_bytes;
+}
+
+/* X::resetDemodulator of one of the four demodulators behind the IqDataProcessor (hrfd_rx_reset_demod) */
+void orc_rx_reset_demod(orc_rx *h, int mode)
+{
+  switch (mode)
+  {
+    case ORC_AM: orc_demod_reset(&h->am); break;
+    case ORC_FM: orc_demod_reset(&h->fm); break;
+    case ORC_WBFM: orc_demod_reset(&h->wbfm); break;
+    case ORC_LSB:
+    case ORC_USB: orc_demod_reset(&h->ssb); break;
+    default: break;
+  }
+}
+
+uint32_t orc_rx_process(orc_rx *h, const int8_t *iq, uint32_t bytes, uint32_t gain_db,
+                        int16_t *pcm, uint32_t pcm_cap, uint32_t *magnitude,
+                        int *signal_allowed, int8_t *iq256_out)
+{
+  uint32_t dec_bytes, n_pcm = 0;
+  int8_t *dec = (int8_t *)calloc((size_t)bytes / 8 + 16, 1);
+  int present, allowed;
+  uint32_t mag_sum = 0, mag_n;
+  int32_t dbfs;
+
+  dec_bytes = rx_front_end(h, iq, bytes, dec);
 
   /* A5: SignalDetector::detectSignal (:205-274) */
   mag_n = dec_bytes / 2;
@@ -889,7 +924,7 @@ uint32_t orc_rx_process(orc_rx *h, const int8_t *iq, uint32_t bytes, uint32_t ga
     }
     free(tmp);
   }
-  free(x); free(t1); free(t2); free(t3); free(dec);
+  free(dec);
   return n_pcm;
 }
 

@@ -43,6 +43,11 @@ void orc_rx_set_threshold(orc_rx *h, int32_t threshold);
 uint32_t orc_rx_process(orc_rx *h, const int8_t *iq, uint32_t bytes, uint32_t gain_db,
                         int16_t *pcm, uint32_t pcm_cap, uint32_t *magnitude,
                         int *signal_allowed, int8_t *iq256_out);
+/* IqDataProcessor::reduceSampleRate as a call of its own, with the Fs/4 mix (hrfd_rx_reduce_sample_rate): the front end
+ * advances, the squelch tracker and the demodulators do not.  iq256_out: 2 * ceil(bytes / 16) bytes; returns the count. */
+uint32_t orc_rx_reduce_sample_rate(orc_rx *h, const int8_t *iq, uint32_t bytes, int8_t *iq256_out);
+/* X::resetDemodulator of the demodulator of `mode` behind the IqDataProcessor (hrfd_rx_reset_demod). */
+void orc_rx_reset_demod(orc_rx *h, int mode);
 /* WBFM float stream of the last call (WbFmDemodulator::demodulatedData). */
 uint32_t orc_rx_wbfm_float_stream(orc_rx *h, float *out, uint32_t cap);
 

@@ -62,6 +62,9 @@ class Oracle:
                                      _u32p, C.POINTER(C.c_int), _i8p]
         L.orc_rx_wbfm_float_stream.restype = C.c_uint32
         L.orc_rx_wbfm_float_stream.argtypes = [C.c_void_p, _f32p, C.c_uint32]
+        L.orc_rx_reduce_sample_rate.restype = C.c_uint32
+        L.orc_rx_reduce_sample_rate.argtypes = [C.c_void_p, _i8p, C.c_uint32, _i8p]
+        L.orc_rx_reset_demod.argtypes = [C.c_void_p, C.c_int]
         L.orc_demod_create.restype = C.c_void_p
         L.orc_demod_create.argtypes = [C.c_int]
         L.orc_demod_destroy.argtypes = [C.c_void_p]
@@ -233,6 +236,17 @@ class _OrcRx:
         count = 2 * ((self.pending + len(iq) // 2) // 8)
         self.pending = (self.pending + len(iq) // 2) % 8
         return pcm[:n].copy(), int(mag.value), bool(allowed.value), iq256[:count]
+
+    def reset_demod(self, mode):
+        self.lib.orc_rx_reset_demod(self.h, mode)
+
+    def reduce_sample_rate(self, iq):
+        """the front end alone -> (byte count, the 256 kS/s bytes WITH the Fs/4 mix: what a mode-NONE call dumps)"""
+        iq = np.ascontiguousarray(iq, dtype=np.int8)
+        out = np.zeros(iq256_capacity(len(iq)) + 16, dtype=np.int8)
+        n = self.lib.orc_rx_reduce_sample_rate(self.h, _p(iq, _i8p), len(iq), _p(out, _i8p))
+        self.pending = (self.pending + len(iq) // 2) % 8
+        return int(n), out[:n].copy()
 
     def wbfm_float_stream(self, count):
         out = np.zeros(count, dtype=np.float32)
