@@ -274,6 +274,18 @@ def load() -> C.CDLL:
         L.hrfd_level_reset.argtypes = [_vp, C.c_uint32]
         L.hrfd_level_process.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]
         L.hrfd_level_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]
+    if hasattr(L, "hrfd_dcs_create"):                      # (an older build named by HRFD_LIB has no DCS bank)
+        L.hrfd_dcs_create.argtypes = [C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_dcs_destroy.argtypes = [_vp]
+        L.hrfd_dcs_set_taps.argtypes = [_vp, _vp, C.c_uint32]
+        L.hrfd_dcs_set_codes.argtypes = [_vp, _vp, _vp, _vp, C.c_uint32]
+        L.hrfd_dcs_n_codes.argtypes = [_vp, _u32p]
+        L.hrfd_dcs_set_min_hits.argtypes = [_vp, C.c_uint32, C.c_uint32]
+        L.hrfd_dcs_reset.argtypes = [_vp, C.c_uint32]
+        L.hrfd_dcs_process.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]
+        L.hrfd_dcs_process_device.argtypes = [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, _vp]
+        L.hrfd_dcs_code_word.argtypes = [C.c_uint32, C.c_int, _u32p, _u32p]
+        L.hrfd_dcs_debug_slow.argtypes = [_vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]
     if hasattr(L, "hrfd_tonegen_create"):                  # (an older build named by HRFD_LIB has no tone generator bank)
         _u64p = C.POINTER(C.c_uint64)
         L.hrfd_tonegen_create.argtypes = [C.c_uint32, C.c_int, C.POINTER(_vp)]

@@ -1474,6 +1474,145 @@ class Leveler(_Bank):
                    _ptr(d_gain), _ptr(d_peak), _ptr(stream))
 
 
+DCS_MAX_TAPS = 512
+DCS_MAX_CODES = 128
+DCS_MAX_BLOCKS = 1024
+DCS_NO_BEST = 255                  # best of a group without entries
+DCS_WORD_BITS = 23
+DCS_GENERATOR = 0xC75              # the (23,12) Golay code's g, bit i = x^i
+DCS_BIT_NUM, DCS_BIT_DEN = 1250, 21        # samples per bit: 8000 / 134.4
+
+
+def dcs_word(code: int, inverted: bool = False) -> int:
+    """the 23-bit word of a DCS code (three octal digits, 0..0o777): (p << 12) | 0x800 | code with p the remainder of
+    (0x800 | code) x^11 modulo DCS_GENERATOR; the complement in 23 bits where inverted.  dcs_word(0o023) == 0x763813"""
+    code = int(code)
+    if not 0 <= code <= 0o777:
+        raise ValueError(f"a DCS code has three octal digits (0..0o777), got {code}")
+    data = 0x800 | code
+    p = data << 11
+    for i in range(22, 10, -1):
+        if p >> i & 1:
+            p ^= DCS_GENERATOR << (i - 11)
+    w = p << 12 | data
+    return w ^ 0x7FFFFF if inverted else w
+
+
+def dcs_canonical(word: int) -> int:
+    """the least of the 23 rotations of a word: what the bank compares, since every sample phase sees a rotation"""
+    w = int(word) & 0x7FFFFF
+    return min(((w >> r) | (w << (23 - r))) & 0x7FFFFF for r in range(23))
+
+
+def dcs_aliases(code: int):
+    """(same, inverse): the codes a receiver cannot tell from `code`, itself among them, and the codes whose inverted form
+    it cannot tell from it.  dcs_aliases(0o023) == ([0o023, 0o340, 0o766], [0o047, 0o375, 0o707]).  A list for Dcs.set_codes
+    may hold one of the six only"""
+    c = dcs_canonical(dcs_word(code))
+    return ([k for k in range(512) if dcs_canonical(dcs_word(k)) == c],
+            [k for k in range(512) if dcs_canonical(dcs_word(k, True)) == c])
+
+
+def dcs_lowpass_taps(T: int = 255, cutoff_hz: float = 300.0) -> np.ndarray:
+    """T int16 taps in Q14 for Dcs.set_taps that keep the sub-audible band and take the voice out: a sinc low-pass at
+    cutoff_hz under np.blackman, normalised to unity at DC, round(h * 16384).  A design aid on the host like
+    audio_highpass_taps, not part of the bank's exact contract."""
+    T = int(T)
+    if T < 1 or T > DCS_MAX_TAPS:
+        raise ValueError(f"T must be 1..{DCS_MAX_TAPS}, got {T}")
+    n = np.arange(T, dtype=np.float64) - (T - 1) / 2
+    low = np.sinc(2.0 * float(cutoff_hz) / TONE_FS * n) * (np.blackman(T) if T > 2 else np.ones(T))
+    low /= low.sum()
+    return np.floor(low * 16384.0 + 0.5).astype(np.int16)
+
+
+def dcs_levels(code: int, n: int, amplitude: int, t0: int = 0, inverted: bool = False) -> np.ndarray:
+    """n int16 samples of a DCS code as it is sent, from stream time t0 on: +amplitude where bit floor(21 t / 1250) mod 23
+    of the word is 1, -amplitude where it is 0 (bit 0 goes first, 134.4 bit/s).  The transmit side until a generator track
+    exists: add it to the voice PCM on the host."""
+    a = int(amplitude)
+    if not 0 <= a <= 32767:
+        raise ValueError(f"amplitude must be 0..32767, got {a}")
+    w = dcs_word(code, inverted)
+    t = np.arange(int(t0), int(t0) + int(n), dtype=np.int64)
+    bit = (w >> ((t * DCS_BIT_DEN // DCS_BIT_NUM) % DCS_WORD_BITS)) & 1
+    return np.where(bit == 1, a, -a).astype(np.int16)
+
+
+class Dcs(_Bank):
+    """The DCS bank (hrfd_dcs_*): the PCM of n_channels channels as Rx / Ddc.receive write it in; per block, how many samples
+    end a 23-bit word of each listed code (hits) and the tone bank's kind of verdict over them (best, present), which
+    Audio.gate / Audio.gate_device take unchanged at frame_len = 512.  No clock recovery: a word is 23 slicer bits on a
+    fixed grid behind a sample.  Exact in integers, independent of how a stream is cut into calls.  (One launch of one
+    workgroup per channel, like Leveler: no chunked launch and no debug_set_max_wgs.)"""
+
+    _prefix = "dcs"
+
+    def __init__(self, n_channels: int, device: int = -1):
+        self.n = int(n_channels)
+        self._create(self.n, device)
+
+    def set_taps(self, taps):
+        """1..512 int16 taps in Q14 with sum |h| <= 65535, one list for every channel (dcs_lowpass_taps designs one); zeroes
+        every channel's state"""
+        t = np.ascontiguousarray(taps, dtype=np.int16).ravel()
+        self._call("set_taps", _ptr(t), t.size)
+
+    def set_codes(self, codes, inverted=None, groups=None):
+        """the whole list, 0..128 entries: codes 0..0o777, inverted (bools) and groups (0..3) per entry or None; two aliases in
+        one list are refused.  Keeps the channels' state"""
+        c = np.ascontiguousarray(codes).ravel()
+        if c.size and (c.min() < 0 or c.max() > 65535):
+            raise ValueError("a code must fit uint16")
+        c = c.astype(np.uint16)
+        inv = None if inverted is None else np.ascontiguousarray(inverted).ravel().astype(bool).astype(np.uint8)
+        grp = None if groups is None else np.ascontiguousarray(groups).ravel()
+        if grp is not None:
+            if grp.size and (grp.min() < 0 or grp.max() > 255):
+                raise ValueError("a group must fit uint8")
+            grp = grp.astype(np.uint8)
+        for name, a in (("inverted", inv), ("groups", grp)):
+            if a is not None and a.size != c.size:
+                raise ValueError(f"{c.size} codes but {a.size} {name}")
+        self._call("set_codes", _ptr(c), _ptr(inv), _ptr(grp), c.size)
+
+    def n_codes(self) -> int:
+        v = C.c_uint32(0)
+        self._call("n_codes", C.byref(v))
+        return int(v.value)
+
+    def set_min_hits(self, group: int = ALL, n: int = 128):
+        """the samples of a block of 512 that must match a group's best entry for it to be present, 1..512, of one group
+        or of all"""
+        self._call("set_min_hits", int(group), int(n))
+
+    def reset(self, channel: int = ALL):
+        """zero the state of one channel, or of all"""
+        self._call("reset", int(channel))
+
+    def process(self, pcm: np.ndarray, n_pcm=None):
+        """pcm int16 [n_channels, n_blocks, 512], n_pcm uint32 [n_channels, n_blocks] or None -> (hits uint16 [n_channels,
+        n_blocks, K], best uint8 [n_channels, n_blocks, 4], present uint8 [n_channels, n_blocks, 4]); blocking"""
+        x = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.n, -1)
+        n_blocks = x.shape[1] // 512
+        if x.shape[1] != 512 * n_blocks:
+            raise ValueError(f"a channel's PCM must be whole blocks of 512 samples, got {x.shape[1]} samples")
+        npc = None if n_pcm is None else np.ascontiguousarray(n_pcm, dtype=np.uint32).reshape(self.n, n_blocks)
+        hits = np.zeros((self.n, n_blocks, self.n_codes()), dtype=np.uint16)
+        best = np.zeros((self.n, n_blocks, TONE_GROUPS), dtype=np.uint8)
+        present = np.zeros((self.n, n_blocks, TONE_GROUPS), dtype=np.uint8)
+        self._call("process", _ptr(x), _ptr(npc), n_blocks, _ptr(hits) if hits.size else None, _ptr(best), _ptr(present))
+        return hits, best, present
+
+    def process_device(self, d_pcm, channel_stride: int, d_n_pcm, n_blocks: int, d_hits=None, d_best=None, d_present=None,
+                       stream=None):
+        """device pointers (ints); d_n_pcm and any output may be None (not all three outputs); d_hits takes uint16
+        [n_channels, n_blocks, K], d_best and d_present uint8 [n_channels, n_blocks, 4], all dense; asynchronous on stream
+        (None = the handle's own)"""
+        self._call("process_device", _ptr(d_pcm), int(channel_stride), _ptr(d_n_pcm), int(n_blocks), _ptr(d_hits), _ptr(d_best),
+                   _ptr(d_present), _ptr(stream))
+
+
 TONEGEN_TRACKS = 2
 TONEGEN_MAX_SEGMENTS = 32
 TONEGEN_MAX_BLOCKS = 1024

@@ -940,6 +940,76 @@ int hrfd_level_process_device(hrfd_level *l, const int16_t *d_pcm, uint64_t chan
                               void *stream);
 
 /* ------------------------------------------------------------------------------
+ * DCS bank: digital coded squelch ("DPL") decoded on the PCM of C channels, the digital sibling of the tone bank's CTCSS.  It
+ * reads what hrfd_rx_process_device / hrfd_ddc_receive write: PCM rows [C][n_blocks][512] int16 at 8 kS/s and, optionally,
+ * n_pcm [C][n_blocks].  A DCS word is 23 bits sent cyclically at 134.4 bit/s, 8000 / 134.4 = 1250 / 21 samples a bit, and a
+ * transmitter's clock stays within a small part of a bit over the 171 ms of a word: so the bank recovers no clock.  The word
+ * that ends at sample m is 23 slicer bits on a fixed grid behind m, every sample has one, and a block's verdict is a count of
+ * samples.  Exact integer arithmetic without a recurrence or a tolerance, the same on every device and however a stream is
+ * cut into calls (tests/dcs_model.py restates it).  Everything is per channel:
+ *   sizes     C = 1..65536 channels, fixed at create; T = 1..HRFD_DCS_MAX_TAPS = 512 taps and K = 0..HRFD_DCS_MAX_CODES = 128
+ *             list entries, one list of each for the bank; n_blocks = 1..HRFD_DCS_MAX_BLOCKS = 1024.
+ *   input     x[m] = sample m of the channel's stream, or 0 where n_pcm is given and the sample's position in its block is
+ *             >= min(n_pcm[c][b], 512) (the level bank's rule; stream time advances 512 a block regardless), and 0 before
+ *             the stream's start or behind hrfd_dcs_reset.
+ *   slicer    acc[m] = sum_{j<T} h[j] x[m-j], h int16 in Q14 with sum |h| <= 65535, so acc is exact in int32;
+ *             s[m] = 1 if acc[m] > 0, else 0.  No rounding, no hysteresis.  A new handle has the single tap 16384.
+ *   word      D[k] = floor(1250 k / 21), k = 0..22 (D[0] = 0, D[22] = 1309); w[m] = sum_k s[m - D[k]] << (22 - k): the
+ *             newest bit is bit 22.  DCS sends bit 0 first, so an aligned window reads the word as written.
+ *   canonical c[m] = the least of the 23 rotations of w[m] within 23 bits.  The (23,12) Golay code is cyclic: every sample
+ *             phase sees a rotation of the word sent, and this step removes the phase.
+ *   codes     word(code), code = 0..511 (three octal digits), = (p << 12) | 0x800 | code, p the 11-bit remainder of
+ *             (0x800 | code) x^11 modulo g = 0xC75 (bit i = x^i): word(023) = 0x763813.  An inverted code is the complement
+ *             in 23 bits.  Entries with one canonical word are aliases (023 = 340 = 766; D023I = D047N): a list that holds
+ *             two is refused, so a sample matches at most one entry.
+ *   hits      hits[b][k] = the number of the 512 positions m of block b with c[m] == canonical(entry k), 0..512.
+ *   verdict   best[b][g] = the entry of group g (0..3) with the most hits, the lowest index on a tie, also when all are 0;
+ *             present[b][g] = hits[b][best] >= min_hits[g], min_hits = 1..512 per group, 128 unless set.  A group without
+ *             entries has best HRFD_DCS_NO_BEST = 255 and present 0, as in the tone bank.  best and present are laid out
+ *             [C][n_blocks][4] uint8, the tone bank's at frame_len = 512: hrfd_audio_gate / hrfd_audio_gate_device take them
+ *             unchanged, with `want` an index into the code list.
+ *   state     per channel the last 512 inputs and the last 1312 slicer bits (1309 are read); read at a call's start,
+ *             replaced at its end.  A stream cut into calls anywhere on block boundaries gives the outputs of one call.
+ * Left out: bit-error tolerance, the 134.4 Hz turn-off code, per-channel lists, DC removal beyond what the taps do,
+ * debouncing over blocks, a generator on the device.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well).  Setters never wait for the device:
+ * what a setter changed is copied to the device on the next call's stream, ahead of its launch.  Calls may use different
+ * streams: each launch is ordered on the device behind the handle's previous one.
+ *   hrfd_dcs_set_taps        T taps; zeroes every channel's state (as hrfd_audio_set_taps)
+ *   hrfd_dcs_set_codes       the whole list: codes [n], inverted [n] (0 / not 0) or NULL (none), groups [n] (0..3) or NULL (all
+ *                            0); n = 0 clears it.  Keeps the state: the slicer bits are facts about the signal
+ *   hrfd_dcs_n_codes         K
+ *   hrfd_dcs_set_min_hits    group: 0..3 or HRFD_ALL_CHANNELS (every group); n = 1..512
+ *   hrfd_dcs_reset           the state of one channel, or of all (HRFD_ALL_CHANNELS), from the next call on
+ *   hrfd_dcs_process         host buffers, dense: pcm [C][n_blocks][512], n_pcm [C][n_blocks] or NULL -> hits uint16
+ *                            [C][n_blocks][K], best and present uint8 [C][n_blocks][4]; any output may be NULL, but not all
+ *                            three; blocking
+ *   hrfd_dcs_process_device  device buffers; input rows channel_stride_bytes apart (even and >= 1024 n_blocks), d_pcm and
+ *                            d_hits at any even address, d_n_pcm 4-byte aligned, the outputs dense.  Asynchronous on `stream`
+ *                            (a hipStream_t, NULL = the handle's own)
+ *   hrfd_dcs_code_word       on the host: word(code), complemented where inverted != 0, and its canonical word; either
+ *                            result may be NULL, not both
+ */
+typedef struct hrfd_dcs hrfd_dcs;
+#define HRFD_DCS_MAX_TAPS 512
+#define HRFD_DCS_MAX_CODES 128
+#define HRFD_DCS_MAX_BLOCKS 1024
+#define HRFD_DCS_GROUPS 4
+#define HRFD_DCS_NO_BEST 255
+int hrfd_dcs_create(uint32_t n_channels, int device, hrfd_dcs **out);
+int hrfd_dcs_destroy(hrfd_dcs *d);
+int hrfd_dcs_set_taps(hrfd_dcs *d, const int16_t *taps, uint32_t n);
+int hrfd_dcs_set_codes(hrfd_dcs *d, const uint16_t *codes, const uint8_t *inverted, const uint8_t *groups, uint32_t n);
+int hrfd_dcs_n_codes(hrfd_dcs *d, uint32_t *n);
+int hrfd_dcs_set_min_hits(hrfd_dcs *d, uint32_t group, uint32_t n);
+int hrfd_dcs_reset(hrfd_dcs *d, uint32_t channel);
+int hrfd_dcs_process(hrfd_dcs *d, const int16_t *pcm, const uint32_t *n_pcm, uint32_t n_blocks, uint16_t *hits, uint8_t *best,
+                     uint8_t *present);
+int hrfd_dcs_process_device(hrfd_dcs *d, const int16_t *d_pcm, uint64_t channel_stride_bytes, const uint32_t *d_n_pcm,
+                            uint32_t n_blocks, uint16_t *d_hits, uint8_t *d_best, uint8_t *d_present, void *stream);
+int hrfd_dcs_code_word(uint32_t code, int inverted, uint32_t *word, uint32_t *canonical);
+
+/* ------------------------------------------------------------------------------
  * Tone generator bank: signalling on the PCM of C transmit channels: CTCSS sub-tones, DTMF digits, tone bursts and paging
  * sequences, added to the rows that hrfd_mod_* and hrfd_duc_transmit read.  The mirror of the tone bank: it sends on the
  * detector's own phase grid.  PCM rows [C][n_blocks][512] int16 at 8 kS/s; there is no n_pcm (transmit PCM has none), and

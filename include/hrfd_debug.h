@@ -100,6 +100,17 @@ int hrfd_hdlc_debug_slow(const uint32_t *limits3, const uint8_t *bits, uint32_t 
                          uint32_t out_bytes, uint32_t *counts3);
 int hrfd_hdlc_debug_max_out(uint32_t max_bits, uint32_t min_payload, uint32_t max_payload, uint32_t *out_bytes);
 
+/* the DCS bank's law as the host states it (hrfd_dcs.h), no device needed; host pointers.
+ *   slow: the contract's loop over ONE channel and one call.  taps [n_taps]; codes, inverted, groups [n_codes] as
+ *         hrfd_dcs_set_codes takes them (an alias is refused alike); min_hits4: one per group; pcm [n_blocks][512], n_pcm
+ *         [n_blocks] or NULL; state300: the channel's 300 dwords (256 of sample pairs, the oldest first; 41 of slicer bits, the
+ *         oldest in bit 0 of the first; 3 of zeros), zero for a fresh channel, read and replaced; hits [n_blocks][n_codes],
+ *         best and present [n_blocks][4] as hrfd_dcs_process gives them for the channel, each or NULL but not all.
+ * tests/test_dcs_model.py holds tests/dcs_model.py against it. */
+int hrfd_dcs_debug_slow(const int16_t *taps, uint32_t n_taps, const uint16_t *codes, const uint8_t *inverted, const uint8_t *groups,
+                        uint32_t n_codes, const uint32_t *min_hits4, const int16_t *pcm, const uint32_t *n_pcm, uint32_t n_blocks,
+                        uint32_t *state300, uint16_t *hits, uint8_t *best, uint8_t *present);
+
 /* ------------------------------------------------------------------ behaviour-changing hooks (HRFD_DEBUG_HOOKS=1) */
 int hrfd_rx_debug_set_atan(hrfd_rx *h, int mode);        /* -1 automatic, 0 table gather, 1 arithmetic */
 int hrfd_rx_debug_set_warm(hrfd_rx *h, int warm);        /* shrink the de-emphasis warm-up, seeds off: forces repairs */
