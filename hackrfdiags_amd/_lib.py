@@ -299,6 +299,22 @@ def load() -> C.CDLL:
         L.hrfd_tonegen_get_clips.argtypes = [_vp, C.c_uint32, _u64p]
         L.hrfd_tonegen_process.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp]
         L.hrfd_tonegen_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp]
+    if hasattr(L, "hrfd_dcsgen_create"):                   # (an older build named by HRFD_LIB has no DCS generator bank)
+        _u64p = C.POINTER(C.c_uint64)
+        L.hrfd_dcsgen_create.argtypes = [C.c_uint32, C.c_int, C.POINTER(_vp)]
+        L.hrfd_dcsgen_destroy.argtypes = [_vp]
+        L.hrfd_dcsgen_set_taps.argtypes = [_vp, _vp, C.c_uint32]
+        L.hrfd_dcsgen_queue.argtypes = [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint64]
+        L.hrfd_dcsgen_cut.argtypes = [_vp, C.c_uint32, C.c_int]
+        L.hrfd_dcsgen_reset.argtypes = [_vp]
+        L.hrfd_dcsgen_set_time.argtypes = [_vp, C.c_uint64]
+        L.hrfd_dcsgen_time.argtypes = [_vp, _u64p]
+        L.hrfd_dcsgen_pending.argtypes = [_vp, C.c_uint32, _u32p, _u64p]
+        L.hrfd_dcsgen_get_clips.argtypes = [_vp, C.c_uint32, _u64p]
+        L.hrfd_dcsgen_process.argtypes = [_vp, _vp, C.c_uint32, _vp, _vp]
+        L.hrfd_dcsgen_process_device.argtypes = [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp]
+        L.hrfd_dcsgen_debug_slow.argtypes = [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _u64p]
+        L.hrfd_dcsgen_debug_edit.argtypes = [_vp, _u32p, C.c_uint64, C.c_int, _vp, C.c_uint32, C.c_uint64]
     if hasattr(L, "hrfd_afsk_create"):                     # (an older build named by HRFD_LIB has no AFSK bank)
         L.hrfd_afsk_create.argtypes = [C.c_uint32, C.c_int, C.POINTER(_vp)]
         L.hrfd_afsk_destroy.argtypes = [_vp]

@@ -1528,8 +1528,9 @@ def dcs_lowpass_taps(T: int = 255, cutoff_hz: float = 300.0) -> np.ndarray:
 
 def dcs_levels(code: int, n: int, amplitude: int, t0: int = 0, inverted: bool = False) -> np.ndarray:
     """n int16 samples of a DCS code as it is sent, from stream time t0 on: +amplitude where bit floor(21 t / 1250) mod 23
-    of the word is 1, -amplitude where it is 0 (bit 0 goes first, 134.4 bit/s).  The transmit side until a generator track
-    exists: add it to the voice PCM on the host."""
+    of the word is 1, -amplitude where it is 0 (bit 0 goes first, 134.4 bit/s).  The host restatement of the DcsGen bank's law
+    under its default tap: what DcsGen writes for the code, generate only, at the stream times t0 .. t0 + n - 1 (21 t must fit
+    int64 here).  DcsGen is the transmit side; this is for tests and for a host that has no device at hand."""
     a = int(amplitude)
     if not 0 <= a <= 32767:
         raise ValueError(f"amplitude must be 0..32767, got {a}")
@@ -1650,7 +1651,7 @@ def _tonegen_segs(segs) -> np.ndarray:
 
 
 class _GenBank(_Bank):
-    """What ToneGen and AfskGen share beyond _Bank: the clock, the clip counters and the process calls of a generator on
+    """What ToneGen, AfskGen and DcsGen share beyond _Bank: the clock, the clip counters and the process calls of a generator on
     transmit PCM.  _max_blocks is the bank's limit on the blocks of a call."""
     _max_blocks = 0
 
@@ -1762,6 +1763,87 @@ class ToneGen(_GenBank):
         n, gap = tonegen_samples(ms_each), tonegen_samples(gap_ms)
         segs = [tonegen_segment(n, hz, amplitude, gap=gap if i else 0) for i, hz in enumerate(hz_list)]
         self.queue(channel, track, segs, start)
+
+
+DCSGEN_MAX_SEGMENTS = 8
+DCSGEN_MAX_BLOCKS = 1024
+DCSGEN_MAX_TAPS = 512
+DCSGEN_FOREVER = 0xFFFFFFFF
+DCSGEN_APPEND = 0xFFFFFFFFFFFFFFFF
+DCSGEN_DEFAULT_TAIL = 1440         # 180 ms of turn-off code
+DCSGEN_PERIOD = 28750              # samples after which both grids repeat: 23 words of 1250 samples, 483 bit times
+
+
+def dcsgen_segment(length: int, code: int = None, inverted: bool = False, amplitude: int = 2000, tail: int = DCSGEN_DEFAULT_TAIL,
+                   gap: int = 0, word: int = None):
+    """one segment for DcsGen.queue: (gap, length, tail, word, amp), the word that of a code (dcs_word) or any 23 bits
+    given as `word`"""
+    if (code is None) == (word is None):
+        raise ValueError("a segment needs exactly one of code and word")
+    return (int(gap), int(length), int(tail), dcs_word(code, inverted) if word is None else int(word), int(amplitude))
+
+
+def _dcsgen_segs(segs) -> np.ndarray:
+    try:
+        rows = [[int(v) for v in s] for s in segs]
+    except TypeError:
+        raise ValueError("segments are sequences of five integers (gap, length, tail, word, amp)")
+    if any(len(r) != 5 for r in rows) or any(v < 0 or v > 0xFFFFFFFF for r in rows for v in r):
+        raise ValueError("a segment is five values that fit uint32: gap, length, tail, word, amp")
+    return np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 5)
+
+
+class DcsGen(_GenBank):
+    """The DCS generator bank (hrfd_dcsgen_*): digital coded squelch on the PCM of n_channels transmit channels, the mirror of
+    Dcs.  Segments of a 23-bit word sent cyclically at 134.4 bit/s, each with a tail of the 134.4 Hz turn-off code, are
+    queued per channel at absolute stream times, shaped by one FIR for the bank and added, saturating, to the rows Mod and
+    Duc.transmit read.  The bit grid is a function of the stream time alone, so a code queued again goes on in phase, and the
+    output does not depend on how a stream is cut into calls.  Exact in integers.  (Its kernel is one launch of at most 2^22
+    workgroups, so it has no chunked launch and no debug_set_max_wgs.)"""
+
+    _prefix = "dcsgen"
+    _max_blocks = DCSGEN_MAX_BLOCKS
+
+    def __init__(self, n_channels: int, device: int = -1):
+        self.n = int(n_channels)
+        self._create(self.n, device)
+
+    def set_taps(self, taps):
+        """1..512 int16 taps in Q14 with sum |h| <= 65535, one shaping filter for every channel (dcs_lowpass_taps designs
+        one that keeps the code's edges out of the voice band); from the next call on, the queue and the clock stay"""
+        t = np.asarray(taps).ravel()
+        if t.size and (t.min() < -32768 or t.max() > 32767):
+            raise ValueError("a tap must fit int16")
+        t = np.ascontiguousarray(t, dtype=np.int16)
+        self._call("set_taps", _ptr(t), t.size)
+
+    def queue(self, channel: int, segs, start: int = DCSGEN_APPEND):
+        """1..8 segments (gap, length, tail, word, amp; dcsgen_segment makes one) on one channel or on all (ALL): the first
+        begins at start + its gap, each next one its gap behind the end of the one before, tail included; start
+        DCSGEN_APPEND = max(time, the end of the channel's last segment).  Refused whole if anything is out of order."""
+        a = _dcsgen_segs(segs)
+        self._call("queue", int(channel), _ptr(a), a.shape[0], int(start))
+
+    def send(self, channel: int, code: int, inverted: bool = False, amplitude: int = 2000, length: int = DCSGEN_FOREVER,
+             tail: int = DCSGEN_DEFAULT_TAIL, start: int = DCSGEN_APPEND):
+        """one code, without an end unless length says so: cut(channel) ends it with its turn-off tail"""
+        self.queue(channel, [dcsgen_segment(length, code, inverted, amplitude, tail)], start)
+
+    def cut(self, channel: int = ALL, with_tail: bool = True):
+        """unkey: the code in progress ends now and its turn-off tail follows (with_tail) or nothing does; a tail in
+        progress runs out (with_tail) or ends now; segments not yet begun are dropped"""
+        self._call("cut", int(channel), 1 if with_tail else 0)
+
+    def set_time(self, N: int):
+        """move the clock only; the queues stay"""
+        self._call("set_time", int(N))
+
+    def pending(self, channel: int):
+        """(segments of the channel that have not ended, the end of the last of them: the time itself where there is none,
+        2^64 - 1 behind a FOREVER segment).  A segment has ended 511 samples behind its end: the shaping filter's reach"""
+        n, end = C.c_uint32(0), C.c_uint64(0)
+        self._call("pending", int(channel), C.byref(n), C.byref(end))
+        return int(n.value), int(end.value)
 
 
 AFSK_MAX_WINDOW = 32

@@ -296,10 +296,10 @@ static int bank_reset_history(H *h, const char *who, uint32_t channel)
   return HRFD_OK;
 }
 
-// What a generator bank (hrfd_tonegen, hrfd_afskgen) keeps beside its BankCore: the clock, the watermark of its queues, the
-// clip counters with their lazy clear, the rotated sine table and the staging of the blocking host entry.  Host fields under
-// the handle's core.mu.  The queues, their copy on the device and the kernel are the bank's own: the gen_* functions below
-// take a handle H with core, n_channels and gen, and the bank's launch function
+// What a generator bank (hrfd_tonegen, hrfd_afskgen, hrfd_dcsgen) keeps beside its BankCore: the clock, the watermark of its
+// queues, the clip counters with their lazy clear, the rotated sine table and the staging of the blocking host entry.  Host
+// fields under the handle's core.mu.  The queues, their copy on the device and the kernel are the bank's own: the gen_*
+// functions below take a handle H with core, n_channels and gen, and the bank's launch function
 //   int launch(H *, const int16_t *d_pcm, uint64_t stride, uint32_t n_blocks, int16_t *d_out, uint64_t out_stride,
 //              uint8_t *d_active, hipStream_t st)
 struct GenCore

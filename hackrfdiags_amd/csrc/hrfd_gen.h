@@ -1,8 +1,9 @@
-// hackrfdiags_amd/csrc/hrfd_gen.h -- what the generator banks in front of the transmit chain (hrfd_tonegen, hrfd_afskgen)
-// share and no HIP is needed for: the limits of a call and of the stream time, the law of one sample (sine index, mix, ramp,
-// output with its saturation), and the checks of a stream time, of a process call and of a getter's channel.  hrfd_bank.hip
-// holds the host part both handles embed (GenCore).  Plain C++ like hrfd_pcm.h (tests/cpp/san_tonegen.cc and san_afskgen.cc
-// compile it on the CPU); the includer declares `int fail(int code, const char *fmt, ...)` and the HRFD_* codes first.
+// hackrfdiags_amd/csrc/hrfd_gen.h -- what the generator banks in front of the transmit chain (hrfd_tonegen, hrfd_afskgen and,
+// for the limits, the output and the checks, hrfd_dcsgen) share and no HIP is needed for: the limits of a call and of the
+// stream time, the law of one sample (sine index, mix, ramp, output with its saturation), and the checks of a stream time,
+// of a process call and of a getter's channel.  hrfd_bank.hip holds the host part the handles embed (GenCore).  Plain C++
+// like hrfd_pcm.h (tests/cpp/san_tonegen.cc, san_afskgen.cc and san_dcsgen.cc compile it on the CPU); the includer declares
+// `int fail(int code, const char *fmt, ...)` and the HRFD_* codes first.
 #pragma once
 #include <stdint.h>
 

@@ -970,8 +970,8 @@ int hrfd_level_process_device(hrfd_level *l, const int16_t *d_pcm, uint64_t chan
  *             unchanged, with `want` an index into the code list.
  *   state     per channel the last 512 inputs and the last 1312 slicer bits (1309 are read); read at a call's start,
  *             replaced at its end.  A stream cut into calls anywhere on block boundaries gives the outputs of one call.
- * Left out: bit-error tolerance, the 134.4 Hz turn-off code, per-channel lists, DC removal beyond what the taps do,
- * debouncing over blocks, a generator on the device.
+ * Left out: bit-error tolerance, detecting the 134.4 Hz turn-off code, per-channel lists, DC removal beyond what the taps do,
+ * debouncing over blocks.  The generator is the bank below, hrfd_dcsgen_* (DESIGN.md 3.20).
  * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well).  Setters never wait for the device:
  * what a setter changed is copied to the device on the next call's stream, ahead of its launch.  Calls may use different
  * streams: each launch is ordered on the device behind the handle's previous one.
@@ -1093,6 +1093,98 @@ int hrfd_tonegen_get_clips(hrfd_tonegen *t, uint32_t channel, uint64_t *n);
 int hrfd_tonegen_process(hrfd_tonegen *t, const int16_t *pcm, uint32_t n_blocks, int16_t *out, uint8_t *active);
 int hrfd_tonegen_process_device(hrfd_tonegen *t, const int16_t *d_pcm, uint64_t channel_stride_bytes, uint32_t n_blocks,
                                 int16_t *d_out, uint64_t out_stride_bytes, uint8_t *d_active, void *stream);
+
+/* ------------------------------------------------------------------------------
+ * DCS generator bank: digital coded squelch keyed onto the PCM of C transmit channels, the mirror of the DCS bank: the 23-bit
+ * word of a code sent cyclically at 134.4 bit/s under the voice, the 134.4 Hz turn-off code behind it, both through one
+ * shaping filter, added to the rows that hrfd_mod_* and hrfd_duc_transmit read.  PCM rows [C][n_blocks][512] int16 at 8 kS/s;
+ * there is no n_pcm, and every sample of every block is written.  Exact integer arithmetic, the same on every device
+ * (tests/dcsgen_model.py restates it); shifts are arithmetic.  Everything is per channel:
+ *   sizes     C = 1..65536 channels, fixed at create; n_blocks = 1..HRFD_DCSGEN_MAX_BLOCKS = 1024; at most
+ *             HRFD_DCSGEN_MAX_SEGMENTS = 8 segments per channel that have not ended; T = 1..HRFD_DCSGEN_MAX_TAPS = 512 taps,
+ *             one list for the bank.
+ *   time      the handle keeps one uint64 sample counter N, the stream time of the next call's first sample.  Every call
+ *             advances it by 512 n_blocks, on the host.  Every stream time stays below 2^63.
+ *   grid      u = n mod 28750, n the absolute stream time: 28750 = 23 x 1250 samples are exactly 483 = 21 x 23 bit times, so
+ *             the pattern is periodic in u.  bit(n) = (word >> (floor(21 u / 1250) mod 23)) & 1: bit 0 of the word goes
+ *             first.  The grid is absolute, not relative to a segment's start: a code queued again behind a cut goes on in
+ *             phase.
+ *   turn-off  sq(n) = +1 where floor(42 u / 1250) is even, else -1: a square wave of one bit time per period, 134.4 Hz.
+ *   segment   {gap, length, tail, word, amp}, five uint32, with a start S (uint64 stream time).  word <= 0x7FFFFF: any 23
+ *             bits (hrfd_dcs_code_word makes the one of a code); amp = 0..32767; length L = 1..2^32-2 samples, or
+ *             HRFD_DCSGEN_FOREVER = 0xFFFFFFFF: no end; tail Q = 0..2^32-2 samples of turn-off code behind the code part
+ *             (HRFD_DCSGEN_DEFAULT_TAIL = 1440: 180 ms); E = S + L + Q.  The raw level:
+ *               r[n] = amp (2 bit(n) - 1)   for S <= n < S + L
+ *               r[n] = amp sq(n)            for S + L <= n < E
+ *               r[n] = 0                    where no segment of the channel covers n
+ *             Segments of a channel never overlap; they may abut.
+ *   shaping   acc[n] = sum_{j<T} h[j] r[n-j], h int16 in Q14 with sum |h| <= 65535, so acc is exact in int32 (65535 x 32767
+ *             + 2^13 < 2^31); g[n] = (acc[n] + 2^13) >> 14, not saturated.  A new handle has the single tap 16384: g = r.
+ *             There is no ramp of its own: the filter over the zeros outside a segment is the ramp.
+ *   output    y = sat16(x + g); x is the input sample, or 0 when the call has no input (generate only).  clips[c] counts the
+ *             samples where the saturation changed the value, until hrfd_dcsgen_reset.
+ *   active    optional uint8 [C][n_blocks]: 1 where the block meets [S, E + T - 1) of any segment, so wherever g can be other
+ *             than 0; else 0.  A caller keys a transmitter with it.
+ *   queue     a segment has ended when E + 511 <= N, whatever T is: no later sample reaches it.  Segments that have ended
+ *             leave the queue with the next call, hrfd_dcsgen_queue or hrfd_dcsgen_cut.
+ * The output at stream time n is a pure function of n, the queue, the taps and x: however a stream is cut into calls, it comes
+ * out the same.  With the single tap 16384 and no input, a code's samples are those of the host's restatement, api.dcs_levels.
+ * Arguments are checked before any device is touched (HRFD_EINVAL without a GPU as well).  No setter waits for the device:
+ * what changed is copied to the device on the next call's stream, ahead of its launch, and a call that already runs keeps the
+ * queue and the taps it was launched with.  Calls may use different streams: each launch is ordered on the device behind the
+ * handle's previous one.
+ *   hrfd_dcsgen_set_taps       T taps, from the next call on; the queue and the clock stay (the filter keeps no state: r is a
+ *                              function of the stream time)
+ *   hrfd_dcsgen_queue          n = 1..8 segments on one channel, or on all (HRFD_ALL_CHANNELS).  The first begins at start +
+ *                              segs[0].gap, each next one gap behind the end E of the one before.  start =
+ *                              HRFD_DCSGEN_APPEND: max(N, the last E), per channel.  Refused whole (HRFD_EINVAL, nothing
+ *                              queued on any channel): a start before N, an overlap, anything behind a FOREVER segment, a
+ *                              ninth segment that has not ended, an amp above 32767, a length of 0, a word of 2^23 or more, a
+ *                              tail of 2^32-1, a time at or above 2^63
+ *   hrfd_dcsgen_cut            one channel, or all.  A segment in its code part at N (S <= N < S + L): the code part ends now,
+ *                              L = N - S and E = N + (with_tail ? Q : 0) (kept below 2^63); dropped if S = N.  In its tail:
+ *                              unchanged with with_tail, E = N without.  Not yet begun: dropped.  E <= N: untouched.  No
+ *                              edit changes r before N
+ *   hrfd_dcsgen_reset          empties every queue, N = 0, clips = 0; the taps stay
+ *   hrfd_dcsgen_set_time       moves the clock only: the queues stay
+ *   hrfd_dcsgen_time           N
+ *   hrfd_dcsgen_pending        of one channel: the segments that have not ended at N, and the E of the last of them (N where
+ *                              there is none, UINT64_MAX behind a FOREVER segment); either result may be NULL, not both
+ *   hrfd_dcsgen_get_clips      clips[channel]; blocks until the handle's calls have run
+ *   hrfd_dcsgen_process        host buffers, dense: pcm [C][n_blocks][512] or NULL (generate only) -> out [C][n_blocks][512],
+ *                              active [C][n_blocks] or NULL.  out may be pcm itself; blocking
+ *   hrfd_dcsgen_process_device device buffers; strides, in place, generate only and the overlap rule as
+ *                              hrfd_tonegen_process_device: in place, a stretch of 2048 samples no segment reaches is neither
+ *                              read nor written.  Asynchronous on `stream` (a hipStream_t, NULL = the handle's own)
+ */
+typedef struct hrfd_dcsgen hrfd_dcsgen;
+typedef struct hrfd_dcsgen_segment
+{
+  uint32_t gap;                            /* samples of silence in front of the segment */
+  uint32_t length;                         /* samples of the code, or HRFD_DCSGEN_FOREVER */
+  uint32_t tail;                           /* samples of turn-off code behind them */
+  uint32_t word;                           /* 23 bits, bit 0 first */
+  uint32_t amp;
+} hrfd_dcsgen_segment;
+#define HRFD_DCSGEN_MAX_SEGMENTS 8
+#define HRFD_DCSGEN_MAX_BLOCKS 1024
+#define HRFD_DCSGEN_MAX_TAPS 512
+#define HRFD_DCSGEN_FOREVER 0xffffffffu
+#define HRFD_DCSGEN_DEFAULT_TAIL 1440u
+#define HRFD_DCSGEN_APPEND UINT64_MAX
+int hrfd_dcsgen_create(uint32_t n_channels, int device, hrfd_dcsgen **out);
+int hrfd_dcsgen_destroy(hrfd_dcsgen *t);
+int hrfd_dcsgen_set_taps(hrfd_dcsgen *t, const int16_t *taps, uint32_t n);
+int hrfd_dcsgen_queue(hrfd_dcsgen *t, uint32_t channel, const hrfd_dcsgen_segment *segs, uint32_t n, uint64_t start);
+int hrfd_dcsgen_cut(hrfd_dcsgen *t, uint32_t channel, int with_tail);
+int hrfd_dcsgen_reset(hrfd_dcsgen *t);
+int hrfd_dcsgen_set_time(hrfd_dcsgen *t, uint64_t N);
+int hrfd_dcsgen_time(hrfd_dcsgen *t, uint64_t *N);
+int hrfd_dcsgen_pending(hrfd_dcsgen *t, uint32_t channel, uint32_t *n_segments, uint64_t *end);
+int hrfd_dcsgen_get_clips(hrfd_dcsgen *t, uint32_t channel, uint64_t *n);
+int hrfd_dcsgen_process(hrfd_dcsgen *t, const int16_t *pcm, uint32_t n_blocks, int16_t *out, uint8_t *active);
+int hrfd_dcsgen_process_device(hrfd_dcsgen *t, const int16_t *d_pcm, uint64_t channel_stride_bytes, uint32_t n_blocks,
+                               int16_t *d_out, uint64_t out_stride_bytes, uint8_t *d_active, void *stream);
 
 /* ------------------------------------------------------------------------------
  * AFSK bank: the PCM of C channels -> the packet data on them: audio frequency-shift keying, Bell 202 at 1200 baud (AX.25 /

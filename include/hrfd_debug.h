@@ -111,6 +111,21 @@ int hrfd_dcs_debug_slow(const int16_t *taps, uint32_t n_taps, const uint16_t *co
                         uint32_t n_codes, const uint32_t *min_hits4, const int16_t *pcm, const uint32_t *n_pcm, uint32_t n_blocks,
                         uint32_t *state300, uint16_t *hits, uint8_t *best, uint8_t *present);
 
+/* the DCS generator bank's law and queue rules as the host states them (hrfd_dcsgen.h), no device needed; host pointers.  A
+ * queue is one channel's, at most 8 rows of six uint64 {S, S + L, E, word, amp, tail} in order of their starts, UINT64_MAX for
+ * the S + L and E of a FOREVER segment.
+ *   slow: the contract's loop over ONE channel and one call.  taps [n_taps]; N: the stream time of the call's first sample;
+ *         pcm [n_blocks][512] or NULL; out [n_blocks][512] (may be pcm), active [n_blocks] or NULL, *clips (may be NULL) as
+ *         hrfd_dcsgen_process gives them.
+ *   edit: one edit at the clock N, the queue read and replaced (room for 8 rows): op 0 = hrfd_dcsgen_queue of segs [n] at
+ *         start = arg, with its refusals; 1 = hrfd_dcsgen_cut with with_tail = arg; 2 = what a call does first: the segments
+ *         that have ended leave.
+ * tests/test_dcsgen_model.py holds tests/dcsgen_model.py against both. */
+int hrfd_dcsgen_debug_slow(const int16_t *taps, uint32_t n_taps, const uint64_t *queue6, uint32_t n_queue, uint64_t N,
+                           const int16_t *pcm, uint32_t n_blocks, int16_t *out, uint8_t *active, uint64_t *clips);
+int hrfd_dcsgen_debug_edit(uint64_t *queue6, uint32_t *n_queue, uint64_t N, int op, const hrfd_dcsgen_segment *segs, uint32_t n,
+                           uint64_t arg);
+
 /* ------------------------------------------------------------------ behaviour-changing hooks (HRFD_DEBUG_HOOKS=1) */
 int hrfd_rx_debug_set_atan(hrfd_rx *h, int mode);        /* -1 automatic, 0 table gather, 1 arithmetic */
 int hrfd_rx_debug_set_warm(hrfd_rx *h, int warm);        /* shrink the de-emphasis warm-up, seeds off: forces repairs */
